@@ -30,7 +30,7 @@ extern "C" {
 
 #define M3_F32 0
 #define M3_F16 1
-#define M3_BF16 2            /* every entry point except m3_ffn_fwd (fp16 there) */
+#define M3_BF16 2            /* every entry point */
 
 #define M3_OK 0
 #define M3_ERR_ARG (-1)      /* bad shape / alignment / null pointer */
@@ -44,10 +44,6 @@ int m3_version(void);
 const char *m3_last_error(void);
 /* fills name[0..len) with the gcnArchName of the current device; returns CU count or <0 */
 int m3_device_query(char *name, int len);
-/* 1 when the library was built with `make EXPERIMENTAL=1` (the opt-in kernels the training step never takes are compiled in:
- * m3_ffn_fwd, the weight-stationary variant behind m3_gemm_set_variant, the wide tiles behind m3_wgrad_set_wide), else 0:
- * those three entry points then exist but refuse (M3_ERR_ARG).  No reference counterpart. */
-int m3_experimental(void);
 
 /* ---------------------------------------------------------------- gate (a1-a3)
  * NoisyGate_VMoE.forward, models/moe/ckpt/noisy_gate_vmoe.py:91-93,168,197-207:
@@ -244,47 +240,12 @@ typedef struct {
   const int32_t *row_scale_idx;    /* i32 [M] device or NULL: which row_scale entry slot m takes (before the division) */
 } m3_gemm_args;
 int m3_gemm_nt(const m3_gemm_args *args, void *stream);
-/* Tuning knob, no reference counterpart: which calls of m3_gemm_nt may take the weight-stationary persistent kernel
- * (fp16, K = 384, N % 128 == 0, M >= 1024; csrc/gemm.hip).  ws_mask bits: 0 plain epilogue, 1 GELU + pre-activation
- * output, 2 GELU'(pre) multiply, 3 fp32 residual, 4 grouped calls as well.  Default 0 (the tiled kernels take every
- * call: measured faster inside the training step); -1 re-reads M3_GEMM_WS from the environment.  Results are the same
- * up to fp32 summation order either way. */
-int m3_gemm_set_variant(int ws_mask);
 /* Tuning knob, no reference counterpart: which calls of m3_gemm_nt take the 256 x 256-tile kernel for long contractions
  * (16-bit operands, K * 2 bytes a multiple of 128 and >= 1024, at most 64 groups; csrc/gemm_big.hip - the ViT-Base shapes
  * of BASELINE configs[3] / configs[4]).  0 never, 1 every call the kernel can run, 2 (default) those where it measured faster
  * with streamed operands: K >= 2048 and at least 96 tiles; -1 re-reads M3_GEMM_BIG from the environment.  Results are the same up to fp32
  * summation order either way. */
 int m3_gemm_set_big(int mode);
-
-/* Fused FFN forward (fp16 activations):
- *   Y[crow(m), :] = (residual[crow(m), :] +) GELU(X[arow(m), :] W1[g]^T + b1[g]) W2[g]^T + b2[g]
- * One launch for `_Expert.forward` (models/moe/ckpt/custom_moe_layer.py:36-44: htoh4 -> GELU -> h4toh through
- * FMoELinear :32-33) with the MOEScatter / MOEGather row movement of `_fmoe_general_global_forward` (:263-265)
- * fused into the operand load / the store, and for the dense `Mlp.forward`
- * (models/moe/ckpt/vision_transformer_moe.py:255-261) with Block's residual add (:450).  The hidden activations
- * [rows, H] are never written: this is the forward of the reference's default activation-checkpointing mode
- * (vision_transformer_moe.py:495-524); a backward that recomputes them is not built (the engine's checkpoint mode re-runs
- * the unfused block forward instead).
- * X [*, D] (row stride ldx elements), W1 [G][H][D], W2p [G][D][H] = W2 with the h index permuted inside every
- * aligned group of 32 (position 8a + 4b + c holds h = 16b + 4a + c, a < 4, b < 2, c < 4: M3_CAST_PERM32 of
- * m3_cast_batch), b1 [G][H], b2 [G][D] fp32 (NULL = 0).  Y [*, D] f16 or fp32 (row stride ldy elements);
- * residual fp32 only with fp32 Y.  pre_out / act_out (optional, f16 [rows in slot order][H]): x W1^T + b1 and its
- * GELU, for a backward that keeps the hidden activations instead of recomputing them.  Grouped call: rows are expert-major slots, group g owns
- * [group_offsets[g], group_offsets[g+1]); x_row_idx / y_row_idx as a_row_idx / c_row_idx of m3_gemm_nt.
- * D in {384, 768}; H a multiple of 64; G <= 64. */
-typedef struct {
-  const void *X; int64_t ldx; const int32_t *x_row_idx; int32_t x_row_div;
-  const void *W1; const void *W2p;
-  const float *b1; const float *b2;
-  void *Y; int64_t ldy; int32_t y_dtype; const int32_t *y_row_idx;
-  const float *residual; int64_t ld_res;
-  void *pre_out; void *act_out;    /* f16 [M][H] (row m = slot m), or NULL */
-  int64_t M; int32_t D; int32_t H; int32_t G;
-  const int32_t *group_offsets;    /* [G+1] device, or NULL for dense */
-  int32_t dtype;                   /* M3_F16 */
-} m3_ffn_args;
-int m3_ffn_fwd(const m3_ffn_args *args, void *stream);
 
 /* Weight gradient ("TN", contraction over rows):
  *   dW[g][n, k] (+)= sum_{m in group g} dC[crow(m), n] * A[arow(m), k]
@@ -339,14 +300,6 @@ typedef struct {
   int32_t direct_beta, direct_beta_db;
 } m3_wgrad_args;
 int m3_wgrad_tn(const m3_wgrad_args *args, void *stream);
-/* The output tile (n x k) m3_wgrad_tn uses for a shape - 128 x 128, or, with the wide tiles switched on, for fp16
- * 128 x 384 (K = 384, N >= 768 a multiple of 128) / 384 x 128 (N = 384, K >= 768 a multiple of 128) with one
- * 512-thread workgroup per CU.  Callers that pick `splits` / `units` themselves size them (and the slab workspace
- * splits * G * N * K) for ceil(N / tn) * ceil(K / tk) tiles per group.
- * m3_wgrad_set_wide: tuning knob, no reference counterpart: 1 = wide tiles where they apply, 0 = 128 x 128 everywhere
- * (default: measured no faster inside the training step), -1 = re-read M3_WGRAD_WIDE from the environment.  Switch it
- * before sizing any workspace. */
-int m3_wgrad_set_wide(int on);
 /* Tuning knob, no reference counterpart: which weight-gradient launches take the LDS-DMA kernel (wgrad_dma_kernel,
  * csrc/wgrad.hip: four workgroups per CU, operands global -> LDS directly; fp16 / bf16 / fp32, power-of-two gather divisors, a
  * per-row factor with fp16 / fp32 only).  0 = none (the register-staged kernel everywhere), 2 = every launch the kernel can
@@ -359,6 +312,9 @@ int m3_wgrad_set_dma(int on);
  * 2304, 3072).  1 = on (default), 0 = 128 x 128 everywhere, -1 = re-read M3_WGRAD_BIG.  m3_wgrad_tile reports (256, 256) for the
  * shapes it takes; switch before sizing workspaces.  Same results up to fp32 summation order. */
 int m3_wgrad_set_big(int on);
+/* The output tile (n x k) m3_wgrad_tn uses for a shape: 256 x 256 where m3_wgrad_set_big's kernel takes it, else 128 x 128.
+ * Callers that pick `splits` / `units` themselves size them (and the slab workspace splits * G * N * K) for
+ * ceil(N / tn) * ceil(K / tk) tiles per group. */
 int m3_wgrad_tile(int N, int K, int dtype, int *tn, int *tk);
 /* 1 when m3_wgrad_tn runs a plain call of this shape (one group, no gathers / factor / bias / balanced units / direct mode) with
  * the streaming kernel for K = 16 / 32 - the router's weight, dW_gate = h^T d_logits (custom_moe_layer.py:213-217) - instead of
@@ -459,16 +415,10 @@ int m3_cast_matrix(const float *src, int G, int rows, int cols, int transpose,
  * descs_dev is a DEVICE array of n_desc descriptors; a job writes dst (same layout as src) and/or dst_t
  * (transposed, [g][cols][rows]) - either may be NULL - from one read of src; tile_start = running sum of
  * G * ceil(rows/32) * ceil(cols/32) over the preceding descriptors, total_tiles = the full sum. */
-#define M3_CAST_PERM32 1    /* dst: last index permuted inside aligned groups of 32 (cols % 32 == 0): position
-                               8a + 4b + c holds source column 16b + 4a + c - the k order in which an MFMA 16x16x32
-                               accumulator pair becomes the next product's operand (m3_ffn_fwd) */
-#define M3_CAST_PERM32_T 2  /* the same for the last index (= source row, rows % 32 == 0) of dst_t */
 typedef struct m3_cast_desc {
   const float *src; void *dst; void *dst_t;
   int32_t G, rows, cols;
   int32_t tile_start;
-  int32_t flags;                   /* M3_CAST_PERM32 / M3_CAST_PERM32_T */
-  int32_t pad1;
 } m3_cast_desc;
 int m3_cast_batch(const m3_cast_desc *descs_dev, int n_desc, int total_tiles, int dst_dtype, void *stream);
 /* dst[i] += src[i] (fp32, n elements): sums the flat gradient buffers of task passes that ran

@@ -68,26 +68,9 @@ class WgradArgs(Structure):
     ]
 
 
-class FfnArgs(Structure):
-    _fields_ = [
-        ("X", c_void_p), ("ldx", c_int64), ("x_row_idx", c_void_p), ("x_row_div", c_int32),
-        ("W1", c_void_p), ("W2p", c_void_p),
-        ("b1", c_void_p), ("b2", c_void_p),
-        ("Y", c_void_p), ("ldy", c_int64), ("y_dtype", c_int32), ("y_row_idx", c_void_p),
-        ("residual", c_void_p), ("ld_res", c_int64),
-        ("pre_out", c_void_p), ("act_out", c_void_p),
-        ("M", c_int64), ("D", c_int32), ("H", c_int32), ("G", c_int32),
-        ("group_offsets", c_void_p),
-        ("dtype", c_int32),
-    ]
-
-
-M3_CAST_PERM32, M3_CAST_PERM32_T = 1, 2
-
-
 class CastDesc(Structure):
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("dst_t", c_void_p), ("G", c_int32), ("rows", c_int32),
-                ("cols", c_int32), ("tile_start", c_int32), ("flags", c_int32), ("pad1", c_int32)]
+                ("cols", c_int32), ("tile_start", c_int32)]
 
 
 class GateFwdArgs(Structure):
@@ -142,14 +125,10 @@ SIGNATURES = {
     "m3_ep_dispatch": (c_int, [_I, _V, _V, _V, _V, _L, _V]),
     "m3_ep_return": (c_int, [_I, _V, _V, _V, _V, _L, _V]),
     "m3_gemm_nt": (c_int, [POINTER(GemmArgs), _V]),
-    "m3_experimental": (c_int, []),
-    "m3_gemm_set_variant": (c_int, [_I]),
     "m3_gemm_set_big": (c_int, [_I]),
-    "m3_ffn_fwd": (c_int, [POINTER(FfnArgs), _V]),
     "m3_wgrad_tn": (c_int, [POINTER(WgradArgs), _V]),
     "m3_wgrad_tile": (c_int, [_I, _I, _I, POINTER(c_int), POINTER(c_int)]),
     "m3_wgrad_skinny": (c_int, [_I, _I, _I]),
-    "m3_wgrad_set_wide": (c_int, [_I]),
     "m3_wgrad_set_dma": (c_int, [_I]),
     "m3_wgrad_set_big": (c_int, [_I]),
     "m3_wgrad_reduce": (c_int, [_V, _I, _L, _V, _I, _V, _L, _V, _I, _V]),

@@ -622,19 +622,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void gemm_nt_dma_kernel(const Gemm
 
 using namespace m3;
 
-// weight-stationary variant: mask of the epilogues it may take (bit 0 plain, 1 GELU + pre-activation, 2 GELU' multiply,
-// 3 fp32 residual, bit 4: grouped calls too).  Off by default (see the kernel's header); -1 = take M3_GEMM_WS from the
-// environment at the first call.
-static int g_ws_mode = -1;
-extern "C" int m3_gemm_set_variant(int ws_mask) {
-  M3_REQUIRE(ws_mask >= -1 && ws_mask < 32, "m3_gemm_set_variant: mask %d out of range", ws_mask);
-#ifndef M3_EXPERIMENTAL
-  M3_REQUIRE(ws_mask <= 0, "m3_gemm_set_variant: the weight-stationary kernel is only in EXPERIMENTAL builds (make EXPERIMENTAL=1)");
-#endif
-  g_ws_mode = ws_mask;
-  return M3_OK;
-}
-
 static int g_big_mode = -1;
 extern "C" int m3_gemm_set_big(int mode) {
   M3_REQUIRE(mode >= -1 && mode <= 2, "m3_gemm_set_big: mode %d out of range", mode);
@@ -697,14 +684,6 @@ extern "C" int m3_gemm_nt(const m3_gemm_args *a, void *stream) {
   // 32-bit per-lane byte offsets: A rows (gathered source rows must be < M) and one B group must fit 4 GiB
   M3_REQUIRE((a->M + 1) * a->lda * es < ((int64_t)1 << 32) && (int64_t)a->N * a->ldb * es < ((int64_t)1 << 32),
              "m3_gemm_nt: operand panel exceeds the 4 GiB reach of the 32-bit lane offsets");
-#ifdef M3_EXPERIMENTAL
-  // weight-stationary persistent variant (gemm_ws.hip; opt-in: m3_gemm_set_variant / M3_GEMM_WS; EXPERIMENTAL builds only)
-  if (g_ws_mode < 0) { const char *e = getenv("M3_GEMM_WS"); g_ws_mode = e ? atoi(e) : 0; }
-  if (g_ws_mode) {
-    const int rc = launch_gemm_ws(d, a, mt, g_ws_mode, s);
-    if (rc <= 0) return rc;                     // 0: launched, < 0: error, 1: not a call it takes
-  }
-#endif
   // epilogue kinds (16-bit dtypes; anything else takes the generic epilogue)
   int epi = DMA_EPI_ANY;
   static int epi_mode = -1;                    // M3_GEMM_EPI=0: generic epilogue everywhere (diagnostics)

@@ -304,7 +304,7 @@ __global__ void cast_matrix_kernel(const float *__restrict__ src, int rows, int 
 struct CastDesc {            // = m3_cast_desc
   const float *src; void *dst; void *dst_t;
   int32_t G, rows, cols;
-  int32_t tile_start, flags, pad1;
+  int32_t tile_start;
 };
 
 template <typename T>
@@ -326,33 +326,28 @@ __global__ __launch_bounds__(256) void cast_batch_kernel(const CastDesc *__restr
   const float *src = d.src + goff;
   if (((d.rows | d.cols) & 3) == 0) {
     // rows and columns multiples of 4 (every weight of the model): one 16-byte load per thread (8 threads x 32 rows), 8-byte
-    // stores for the plain copy and - through the LDS tile - for the transposed one.  M3_CAST_PERM32 moves whole groups
-    // of four (source group 4b + a of an aligned 32 -> position group 2a + b), so it acts on the group index.
+    // stores for the plain copy and - through the LDS tile - for the transposed one
     const int tr = threadIdx.x >> 3, tg = threadIdx.x & 7;
-    const int tgp = 2 * (tg & 3) + (tg >> 2);
     const int r = r0 + tr, c = c0 + 4 * tg;
     f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
     if (r < d.rows && c < d.cols) v = *(const f32x4 *)(src + (int64_t)r * d.cols + c);
     if (d.dst && r < d.rows && c < d.cols)
-      Vec4<T>::store((T *)d.dst + goff + (int64_t)r * d.cols + c0 + 4 * ((d.flags & 1) ? tgp : tg), v);
+      Vec4<T>::store((T *)d.dst + goff + (int64_t)r * d.cols + c, v);
     tile[tr][4 * tg + 0] = v[0]; tile[tr][4 * tg + 1] = v[1]; tile[tr][4 * tg + 2] = v[2]; tile[tr][4 * tg + 3] = v[3];
     if (!d.dst_t) return;
     __syncthreads();
     const int cc = c0 + tr, rg = r0 + 4 * tg;                        // dst_t[cc][rg .. rg + 3] = src[rg .. rg + 3][cc]
     if (cc < d.cols && rg < d.rows) {
       const f32x4 w = f32x4{tile[4 * tg + 0][tr], tile[4 * tg + 1][tr], tile[4 * tg + 2][tr], tile[4 * tg + 3][tr]};
-      Vec4<T>::store((T *)d.dst_t + goff + (int64_t)cc * d.rows + r0 + 4 * ((d.flags & 2) ? tgp : tg), w);
+      Vec4<T>::store((T *)d.dst_t + goff + (int64_t)cc * d.rows + rg, w);
     }
     return;
   }
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-  // M3_CAST_PERM32: source index q = 16b + 4a + c of an aligned 32-group goes to position 8a + 4b + c
-  const int txp = ((tx >> 2) & 3) * 8 + (tx >> 4) * 4 + (tx & 3);
-  const int tx_d = (d.flags & 1) ? txp : tx, tx_t = (d.flags & 2) ? txp : tx;
   for (int i = ty; i < 32; i += 8) {
     const int r = r0 + i, c = c0 + tx;
     const float v = (r < d.rows && c < d.cols) ? src[(int64_t)r * d.cols + c] : 0.f;
-    if (d.dst && r < d.rows && c < d.cols) ((T *)d.dst + goff)[(int64_t)r * d.cols + c0 + tx_d] = (T)v;
+    if (d.dst && r < d.rows && c < d.cols) ((T *)d.dst + goff)[(int64_t)r * d.cols + c] = (T)v;
     tile[i][tx] = v;
   }
   if (!d.dst_t) return;
@@ -360,7 +355,7 @@ __global__ __launch_bounds__(256) void cast_batch_kernel(const CastDesc *__restr
   T *dst_t = (T *)d.dst_t + goff;
   for (int i = ty; i < 32; i += 8) {
     const int c = c0 + i, r = r0 + tx;   // dst_t[c][r]
-    if (r < d.rows && c < d.cols) dst_t[(int64_t)c * d.rows + r0 + tx_t] = (T)tile[tx][i];
+    if (r < d.rows && c < d.cols) dst_t[(int64_t)c * d.rows + r] = (T)tile[tx][i];
   }
 }
 

@@ -15,7 +15,7 @@ import torch
 from . import _lib
 from ._lib import M3_ACT_GELU, M3_ACT_NONE, M3_BF16, M3_F16, M3_F32, GemmArgs, WgradArgs, WgradReduceDesc, check, lib
 
-_DT = {torch.float32: M3_F32, torch.float16: M3_F16, torch.bfloat16: M3_BF16}      # bf16: every entry point except the opt-in fused m3_ffn_fwd
+_DT = {torch.float32: M3_F32, torch.float16: M3_F16, torch.bfloat16: M3_BF16}      # bf16: every entry point
 
 
 def dt_code(dtype: torch.dtype) -> int:
@@ -322,63 +322,10 @@ def gemm_nt(A, B, C, *, M=None, bias=None, act=M3_ACT_NONE, pre_out=None, gelu_g
     return C
 
 
-def gemm_set_variant(ws_mask: int):
-    """which gemm_nt calls may take the weight-stationary kernel (include/m3vit_hip.h: m3_gemm_set_variant); 0 = none"""
-    check(lib().m3_gemm_set_variant(int(ws_mask)), "m3_gemm_set_variant")
-
-
 def gemm_set_big(mode: int):
     """which gemm_nt calls take the 256 x 256-tile kernel for long contractions (include/m3vit_hip.h: m3_gemm_set_big):
     0 never, 1 every call it can run, 2 (default) those with enough tiles to fill the chip, -1 re-read M3_GEMM_BIG"""
     check(lib().m3_gemm_set_big(int(mode)), "m3_gemm_set_big")
-
-
-def ffn_supported(D: int, H: int, dtype: torch.dtype, G: int = 1) -> bool:
-    """shapes the fused FFN kernels take (anything else runs the unfused m3_gemm_nt pair)"""
-    return dtype == torch.float16 and D in (384, 768) and H % 64 == 0 and 64 <= H <= 8192 and G <= 64 and \
-        49152 + 64 * (2 if D == 384 else 1) * D * 2 + (H + D) * 4 <= 163840
-
-
-def ffn_fwd(X, W1, W2p, Y, *, b1=None, b2=None, M=None, residual=None, x_row_idx=None, x_row_div=1, y_row_idx=None,
-            group_offsets=None, pre_out=None, act_out=None):
-    """Y[crow(m)] = (residual +) GELU(X[arow(m)] W1[g]^T + b1[g]) W2[g]^T + b2[g] in one launch (m3_ffn_fwd).
-    X [rows, D] f16; W1 [H, D] or [G, H, D]; W2p = W2 [.., D, H] with the PERM32 column order (CastPlan perm flag);
-    Y [rows, D] f16 or f32.  pre_out / act_out (optional, f16 [M, H], slot order): x W1^T + b1 and its GELU."""
-    _req(X, torch.float16, "X"); _req(W1, torch.float16, "W1"); _req(W2p, torch.float16, "W2p"); _req(Y, name="Y")
-    G = 1 if W1.dim() == 2 else W1.shape[0]
-    H, D = W1.shape[-2], W1.shape[-1]
-    assert W2p.shape[-2] == D and W2p.shape[-1] == H
-    a = _lib.FfnArgs()
-    a.X = X.data_ptr(); a.ldx = X.stride(0)
-    a.x_row_idx = x_row_idx.data_ptr() if x_row_idx is not None else None
-    a.x_row_div = x_row_div
-    a.W1 = W1.data_ptr(); a.W2p = W2p.data_ptr()
-    for b, n in ((b1, "b1"), (b2, "b2")):
-        if b is not None:
-            _req(b, torch.float32, n)
-    a.b1 = b1.data_ptr() if b1 is not None else None
-    a.b2 = b2.data_ptr() if b2 is not None else None
-    a.Y = Y.data_ptr(); a.ldy = Y.stride(0); a.y_dtype = dt_code(Y.dtype)
-    a.y_row_idx = y_row_idx.data_ptr() if y_row_idx is not None else None
-    if residual is not None:
-        _req(residual, torch.float32, "residual")
-    a.residual = residual.data_ptr() if residual is not None else None
-    a.ld_res = residual.stride(0) if residual is not None else 0
-    if M is None:
-        M = x_row_idx.numel() if x_row_idx is not None else X.shape[0]
-    for o, n in ((pre_out, "pre_out"), (act_out, "act_out")):
-        if o is not None:
-            _req(o, torch.float16, n)
-            assert o.shape[-1] == H and o.stride(0) == H and o.shape[0] >= M
-    a.pre_out = pre_out.data_ptr() if pre_out is not None else None
-    a.act_out = act_out.data_ptr() if act_out is not None else None
-    a.M = M; a.D = D; a.H = H; a.G = G
-    a.group_offsets = group_offsets.data_ptr() if group_offsets is not None else None
-    a.dtype = M3_F16
-    if M == 0:
-        return Y
-    check(lib().m3_ffn_fwd(byref(a), _stream()), "m3_ffn_fwd")
-    return Y
 
 
 class WgradQueue:
@@ -560,11 +507,6 @@ def _wgrad_slots(dtype, N=0, K=0, G=1, tiles_total=0):
     return 1024 if _wgrad_uses_dma(N, K, G, dtype, tiles_total) else 512
 
 
-def wgrad_set_wide(on: int):
-    """wide weight-gradient tiles on / off (include/m3vit_hip.h: m3_wgrad_set_wide); switch before sizing workspaces"""
-    check(lib().m3_wgrad_set_wide(int(on)), "m3_wgrad_set_wide")
-
-
 def wgrad_set_big(on: int):
     """256 x 256 weight-gradient tiles for the 16-bit ViT-Base shapes: 1 on (default) / 0 off / -1 from M3_WGRAD_BIG
     (include/m3vit_hip.h: m3_wgrad_set_big); switch before sizing workspaces"""
@@ -608,8 +550,7 @@ def default_wgrad_splits(M, N, K, G, dtype=None):
     """Row splits of the TN GEMM.  128 x 128 tiles: fill the 512 resident workgroup slots (2 per CU) exactly once - more
     splits only add slab traffic and a ragged second wave of workgroups - but keep at least _WGRAD_MIN_STEPS 32-row
     steps per split, so that short contractions (few tokens) do not pay a 64 KiB slab write + reduce per handful of
-    steps.  Wide tiles (one 512-thread workgroup per CU, 256 slots): as many splits as fill the slots once; with more
-    tiles than a third of the slots (grouped experts) the split count whose workgroups come closest to whole rounds."""
+    steps."""
     if wgrad_skinny(N, K, G):                       # the router's weight: a stream over dC, 64+ rows per part (16 per wave)
         return int(max(1, min(256, M // 64)))
     tn, tk = wgrad_tile(N, K, dtype)
@@ -623,20 +564,10 @@ def default_wgrad_splits(M, N, K, G, dtype=None):
         most = 128 if dtype == torch.float32 else _WGRAD_MOST16
         sp = int(max(1, min(cap, most, nslots // tiles if tiles <= nslots else 1)))
         return _xcd_aligned(sp) if G == 1 else sp
-    slots = 256
-    if (tn, tk) == (256, 256):
-        # one 8-wave workgroup per CU: fill the 256 slots once; with more tiles than slots (grouped experts) one part per
-        # group - the kernel then accumulates into dW itself (direct mode), no slabs
-        sp = int(max(1, min(cap, 32, slots // tiles))) if tiles < slots else 1
-        return _xcd_aligned(sp) if G == 1 else sp
-    if 3 * tiles <= slots:
-        return int(max(1, min(cap, slots // tiles)))
-    best, best_cost = 1, None
-    for s_ in range(1, min(cap, 8) + 1):
-        cost = -(-tiles * s_ // slots) / s_ * (1 + 0.15 * s_)      # rounds x length of a unit (+ its slab: measured, tools/wgrad_bench.py --splits)
-        if best_cost is None or cost < best_cost:
-            best, best_cost = s_, cost
-    return int(best)
+    # 256 x 256 tiles, one 8-wave workgroup per CU: fill the 256 slots once; with more tiles than slots (grouped experts) one
+    # part per group - the kernel then accumulates into dW itself (direct mode), no slabs
+    sp = int(max(1, min(cap, 32, 256 // tiles))) if tiles < 256 else 1
+    return _xcd_aligned(sp) if G == 1 else sp
 
 
 def colsum(dC, db, *, M=None, beta=0, c_row_idx=None, group_offsets=None, ws=None):
@@ -757,14 +688,13 @@ class CastPlan:
     model, converted by ONE launch per optimizer step."""
 
     def __init__(self, jobs, dst_dtype):
-        # jobs: list of (src fp32 [.., rows, cols], dst [.., rows, cols] or None, dst_t [.., cols, rows] or None[, flags]):
+        # jobs: list of (src fp32 [.., rows, cols], dst [.., rows, cols] or None, dst_t [.., cols, rows] or None):
         # the plain and / or the transposed copy, both written from one read of src
         arr = (_lib.CastDesc * len(jobs))()
         t0 = 0
         self.keep = []
         for d, job in zip(arr, jobs):
-            src, dst, dst_t = job[:3]
-            d.flags = job[3] if len(job) > 3 else 0
+            src, dst, dst_t = job
             _req(src, torch.float32, "src")
             rows, cols = src.shape[-2], src.shape[-1]
             G = src.numel() // (rows * cols)
@@ -773,10 +703,6 @@ class CastPlan:
                     _req(o, dst_dtype, "dst")
                     assert o.numel() == src.numel()
             assert dst is not None or dst_t is not None
-            if d.flags & _lib.M3_CAST_PERM32:
-                assert dst is not None and cols % 32 == 0
-            if d.flags & _lib.M3_CAST_PERM32_T:
-                assert dst_t is not None and rows % 32 == 0
             d.src, d.G, d.rows, d.cols, d.tile_start = src.data_ptr(), G, rows, cols, t0
             d.dst = dst.data_ptr() if dst is not None else None
             d.dst_t = dst_t.data_ptr() if dst_t is not None else None

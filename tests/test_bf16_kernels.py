@@ -5,7 +5,7 @@ rows), operand casts, row gather - against torch fp64 on the same bf16-rounded o
 outputs stored in bf16 are compared at 6e-3, fp32 outputs of bf16 products at 2e-3), and the MoE layer mirror
 (FMoETransformerMLP: gate -> dispatch -> grouped FFN -> combine) forward + backward on bfloat16 input rows; attention
 forward / backward (LDS-resident and streamed kernels); and the fused executor end to end in bf16 against the float64
-oracle.  Only the fused FFN kernel (m3_ffn_fwd) stays fp16."""
+oracle."""
 import numpy as np
 import pytest
 import torch

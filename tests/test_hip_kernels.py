@@ -756,8 +756,9 @@ def test_cast_and_patchify(ops):
     dst2 = torch.empty(3, 70, 45, dtype=torch.float32, device=dev())
     ops.cast_matrix(src, dst2)
     assert torch.equal(dst2, src)
-    # the same through one batched launch (ragged shapes, grouped matrices; plain / transposed / both per job)
-    srcs = [rnd(3, 70, 45, seed=87), rnd(33, 100, seed=88), rnd(1, 5, 7, seed=89), rnd(64, 16, seed=90)]
+    # the same through one batched launch (ragged shapes, grouped matrices; plain / transposed / both per job; the last
+    # job is a grouped one on the 16-byte path, rows and columns multiples of 4)
+    srcs = [rnd(3, 70, 45, seed=87), rnd(33, 100, seed=88), rnd(1, 5, 7, seed=89), rnd(64, 16, seed=90), rnd(3, 64, 96, seed=91)]
     jobs = []
     for i, sm in enumerate(srcs):
         tshape = (*sm.shape[:-2], sm.shape[-1], sm.shape[-2])
