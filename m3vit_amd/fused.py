@@ -8,7 +8,9 @@ allocations and ~1500 Python-issued launches.  FusedBackbone puts the executor b
 
   * the module's nn.Parameters ARE the executor's fp32 masters (same storage); their `.grad` attributes are views of the
     executor's flat gradient buffer, so `optimizer.step()`, `DistributedGroupedDataParallel.allreduce_params()`
-    (fmoe/distributed.py) and `zero_grad(set_to_none=True/False)` work as they do on any module;
+    (fmoe/distributed.py) and `zero_grad(set_to_none=True/False)` work as they do on any module.  Inside a torch
+    DistributedDataParallel forward, with parameter hooks, or with fused_grads="autograd" the parameters are inputs of the
+    node instead and its backward returns their gradients (`_deliver`);
   * one forward = one torch.autograd.Function node (tokens [B, N, D] fp32 and the summed balance loss come out, d tokens
     and d cv_loss go in); every call that is still waiting for its backward owns an executor context ("slot": activations,
     scratch, gradient buffer, HIP stream).  Forward and backward of a slot are captured into hipGraphs at their second
@@ -56,18 +58,30 @@ class _Slot:
 
 
 class _BackboneFn(torch.autograd.Function):
+    """views delivery: inputs (anchor, fb, slot, task_id, images), the gradients go to the .grad views of FusedBackbone.gsum.
+    autograd delivery: the parameters follow as `*params` (FusedBackbone.plist order) and backward returns their gradients"""
+
     @staticmethod
-    def forward(ctx, anchor, fb, slot, task_id, images):
+    def forward(ctx, anchor, fb, slot, task_id, images, *params):
         tok, cv = fb._run_forward(slot, task_id, images)
         ctx.fb, ctx.slot, ctx.task_id = fb, slot, task_id
         ctx.token = _Release(fb, slot)                # returns the slot if this node dies without a backward
+        ctx.autograd = len(params) > 0
+        if ctx.autograd:
+            fb.ag_nodes.append(weakref.ref(ctx))
         return tok, cv
 
     @staticmethod
     def backward(ctx, g_tok, g_cv):
         ctx.token.done = True
-        ctx.fb._run_backward(ctx.slot, ctx.task_id, g_tok, g_cv)
-        return None, None, None, None, None
+        flat = ctx.fb._run_backward(ctx.slot, ctx.task_id, g_tok, g_cv, ctx if ctx.autograd else None)
+        if not ctx.autograd:
+            return None, None, None, None, None
+        need = ctx.needs_input_grad[5:]
+        if flat is None:
+            return (None,) * (5 + len(need))
+        grads = torch._utils._unflatten_dense_tensors(flat, ctx.fb.plist)
+        return (None,) * 5 + tuple(g if n else None for g, n in zip(grads, need))
 
 
 class _Release:
@@ -91,6 +105,7 @@ class FusedBackbone:
         self.dirty = True
         self.anchor = None
         self.names = None
+        self.plist = None
         self._join_queued = False
         import os
         self.prefetch = os.environ.get("M3VIT_PREFETCH", "1") != "0"
@@ -100,6 +115,10 @@ class FusedBackbone:
         self.backward_seen = False
         self.versions_changed = False
         self.e_first, self.e_hist, self.e_pattern, self.e_spec, self.e_version, self.e_backoff = None, [], None, {}, 0, 0
+        self.spec_grads = None
+        # autograd delivery (see _deliver): the nodes still waiting for their backward, the backward call (autograd graph
+        # task) that is summing its passes, and the fresh buffer it sums into
+        self.ag_nodes, self.ag_task, self.ag_acc = [], None, None
 
     # a copy of the model (copy.deepcopy for an EMA twin, torch.save of the whole module) gets no executor state - contexts,
     # streams and graphs are rebuilt at its first call
@@ -111,8 +130,33 @@ class FusedBackbone:
 
     # ------------------------------------------------------------------ eligibility
     @staticmethod
-    def unsupported(model, x, gate_inp, task_id, sem):
-        """None when this call can run on the executor, else the reason it takes the per-op path"""
+    def grads_mode(model):
+        """how a training call delivers the parameter gradients: "views" (the parameters' .grad are views of the sum buffer,
+        written by the executor; no autograd node of a parameter runs) or "autograd" (the parameters are inputs of the node,
+        its backward returns their gradients: AccumulateGrad, tensor hooks, post-accumulate hooks, torch DDP's reducer and
+        torch.autograd.grad see them).  fused_grads="auto" takes "autograd" inside a torch DDP forward that wraps this
+        model and when a trainable parameter carries a hook (DDP's Python reducer registers post-accumulate hooks)"""
+        mode = model.fused_grads
+        if mode != "auto":
+            return mode
+        try:
+            from torch.nn.parallel import DistributedDataParallel
+            ddp = DistributedDataParallel._get_active_ddp_module()
+        except (ImportError, AttributeError):
+            ddp = None
+        if ddp is not None and any(m is model for m in ddp.module.modules()):
+            return "autograd"
+        # (the executor's parameter list once it is built: walking the module tree costs ~0.2 ms of host time per call)
+        fb = model._fused
+        for p in (fb.plist if fb is not None and fb.plist is not None else model.parameters()):
+            if p.requires_grad and (p._backward_hooks or p._post_accumulate_grad_hooks):
+                return "autograd"
+        return "views"
+
+    @staticmethod
+    def unsupported(model, x, gate_inp, task_id, sem, grads="views"):
+        """None when this call can run on the executor, else the reason it takes the per-op path (`grads`: the delivery
+        this call needs, see grads_mode)"""
         if not x.is_cuda:
             return "CPU tensor"
         if model.world_size > 1:
@@ -123,6 +167,8 @@ class FusedBackbone:
             return "caller-supplied gate input"
         if not model._fused_static_ok:
             return model._fused_static_why
+        if grads == "autograd" and model.world_size > 1:
+            return "gradients through autograd (torch DDP, parameter hooks, fused_grads='autograd') with an expert parallel layer"
         if torch.is_grad_enabled() and not model.training:
             return "eval mode with autograd on"
         if torch.is_grad_enabled() and x.requires_grad:
@@ -231,7 +277,7 @@ class FusedBackbone:
         return True
 
     # ------------------------------------------------------------------ forward
-    def forward(self, images, task_id):
+    def forward(self, images, task_id, grads="views"):
         model = self.model()
         B = images.shape[0]
         dev = images.device
@@ -275,7 +321,7 @@ class FusedBackbone:
         if new_step:
             self._close_step()
         # a pass that was started ahead of its call (see _prefetch): hand it over
-        hit = self.spec.pop(task_id, None) if (self.spec and images is self.spec_images and
+        hit = self.spec.pop(task_id, None) if (self.spec and images is self.spec_images and grads == self.spec_grads and
                                                images._version == self.spec_version) else None
         if hit is None and self.spec:
             self._drop_prefetched()                   # the caller did something else than last step: stop predicting for a while
@@ -290,11 +336,11 @@ class FusedBackbone:
             slot.main = main
             self.prefetch_hits += 1
         else:
-            slot = self._launch(task_id, images, main)
+            slot = self._launch(task_id, images, main, grads)
             tok, cv = slot.result
             slot.result = None
             if new_step:
-                self._prefetch(task_id, images, main)
+                self._prefetch(task_id, images, main, grads)
         main.wait_stream(slot.stream)
         tok.record_stream(main)
         cv.record_stream(main)
@@ -317,7 +363,7 @@ class FusedBackbone:
             noises, ps = self._draw(slot, slot.eng)
             if key not in slot.graphs_e:
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                with ops.graph_capture(g):
                     out = slot.eng.forward(slot.images, task_id, noises=noises, path_scales=ps)
                 slot.graphs_e[key] = (g, out)
                 slot.py_owner = ("eval", key)
@@ -377,16 +423,17 @@ class FusedBackbone:
         slot.busy = False
         return tok, cv
 
-    def _launch(self, task_id, images, main):
+    def _launch(self, task_id, images, main, grads):
         """start one task pass on a free slot's stream, ordered behind everything queued on `main` so far; main is NOT made to
         wait for it here"""
+        params = self.plist if grads == "autograd" else ()
         slot = self._slot()
         slot.busy, slot.main = True, main
         s = slot.stream
         s.wait_stream(main)
         try:
             with torch.cuda.stream(s):
-                slot.result = _BackboneFn.apply(self.anchor, self, slot, task_id, images)
+                slot.result = _BackboneFn.apply(self.anchor, self, slot, task_id, images, *params)
         except BaseException:
             slot.busy = False                         # a failed launch must not keep the context
             raise
@@ -427,12 +474,14 @@ class FusedBackbone:
         self.backoff = self.PREFETCH_BACKOFF
         self.prefetch_misses += 1
 
-    def _prefetch(self, task_id, images, main):
+    def _prefetch(self, task_id, images, main, grads):
+        # (in autograd delivery the passes started ahead carry the parameters as inputs like any other; a call that asks for
+        # the other delivery does not take them)
         if not self.prefetch or self.backoff > 0 or not self.pattern or self.pattern[0] != task_id:
             return
-        self.spec_images, self.spec_version = images, images._version
+        self.spec_images, self.spec_version, self.spec_grads = images, images._version, grads
         for t in self.pattern[1:]:
-            slot = self._launch(t, images, main)
+            slot = self._launch(t, images, main, grads)
             tok, cv = slot.result
             slot.result = None
             self.spec[t] = (slot, tok, cv)
@@ -499,7 +548,7 @@ class FusedBackbone:
             noises = slot.noises if (self.cfg.vmoe_noisy_std > 0 and self.model().training) else None
             ps = slot.path_scales if (self.drop and self.model().training) else None
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            with ops.graph_capture(g):
                 if zero:
                     eng.zero_grad()
                 out = eng.forward(slot.images, task_id, noises=noises, path_scales=ps)
@@ -543,7 +592,9 @@ class FusedBackbone:
         for i in fresh + foreign:
             plist[i].grad = views[i]
 
-    def _run_backward(self, slot, task_id, g_tok, g_cv):
+    def _run_backward(self, slot, task_id, g_tok, g_cv, node=None):
+        """views delivery (node None): returns None; autograd delivery: returns the flat gradient buffer to hand to autograd,
+        or None when another pass of this backward call hands over the sum (see _deliver)"""
         eng = slot.eng
         cur = torch.cuda.current_stream()             # autograd: the stream of the node's forward = slot.stream
         gs = self.gstream
@@ -552,7 +603,8 @@ class FusedBackbone:
             cur.wait_stream(slot.stream)
         # the trainer may have consumed / zeroed the gradients on its own stream since the last backward
         gs.wait_stream(slot.main)
-        self._install_grads()
+        if node is None:
+            self._install_grads()
         if slot.dtok is None:
             slot.dtok = torch.zeros(eng.B, eng.N, eng.D, dtype=torch.float32, device=self.device)
         if g_tok is None:
@@ -575,10 +627,16 @@ class FusedBackbone:
             g = slot.graphs_b.get(task_id)
             if g is None:
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                with ops.graph_capture(g):
                     eng.backward(slot.dtok, cv_weight=slot.dcv)
                 slot.graphs_b[task_id] = g
             g.replay()
+        if node is not None:
+            flat = self._deliver(slot, node, cur)
+            slot.busy = False
+            self.dirty = True
+            self.backward_seen = True
+            return flat
         gs.wait_stream(cur)
         with torch.cuda.stream(gs):
             ops.add_f32(self.gsum, eng.flat_grads)
@@ -599,3 +657,41 @@ class FusedBackbone:
     def _join_caller(self):
         self._join_queued = False
         torch.cuda.current_stream().wait_stream(self.gstream)
+
+    def _deliver(self, slot, node, cur):
+        """Autograd delivery of this pass's gradients (slot.eng.flat_grads, final on `cur`).  Autograd keeps what a node
+        returns (AccumulateGrad may make it the .grad itself, DDP copies it into a bucket, a hook may hold it), so what is
+        returned is a buffer allocated for this backward call that no executor launch writes afterwards - never the slot's
+        buffer or gsum.  The passes of ONE backward call (a joint multi-task step) are summed the way views delivery sums
+        them: the first pass the engine runs copies its buffer into a fresh one on the gradient stream, the others add into
+        it there (m3_add_f32, under the other passes' backward kernels); only the last of them - no other pending fused node
+        will still be run by this backward call - returns the sum, the others return None.  A backward call of one pass
+        returns a copy of its buffer.  Either way the returned buffer is complete on `cur`, the stream autograd runs this
+        node on, before the node returns."""
+        gs = self.gstream
+        flat = slot.eng.flat_grads
+        self.ag_nodes = [r for r in self.ag_nodes if r() is not None and r() is not node]
+        task = torch._C._current_graph_task_id()
+        first = self.ag_task != task or self.ag_acc is None
+        last = not any(torch._C._will_engine_execute_node(n) for n in (r() for r in self.ag_nodes) if n is not None)
+        if slot.add_done is None:
+            slot.add_done = torch.cuda.Event()
+        if first and last:
+            self.ag_task = self.ag_acc = None
+            out = flat.clone()
+            slot.add_done.record(cur)                 # (the slot's next forward zeroes its buffer behind this read)
+            return out
+        gs.wait_stream(cur)
+        with torch.cuda.stream(gs):
+            if first:
+                self.ag_acc = flat.clone()
+            else:
+                ops.add_f32(self.ag_acc, flat)
+            slot.add_done.record(gs)
+        if not last:
+            self.ag_task = task
+            return None
+        out, self.ag_task, self.ag_acc = self.ag_acc, None, None
+        cur.wait_stream(gs)
+        out.record_stream(cur)
+        return out

@@ -6,7 +6,9 @@ HIP stream.  No function in this module computes anything with torch ops.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import gc
 from ctypes import byref, c_void_p
 from typing import Optional
 
@@ -31,6 +33,25 @@ def _p(t: Optional[torch.Tensor]):
 
 def _stream():
     return c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+@contextlib.contextmanager
+def graph_capture(g: "torch.cuda.CUDAGraph"):
+    """`torch.cuda.graph(g, capture_error_mode="thread_local")` with Python's cyclic garbage collector held off until the
+    capture has ended.  torch no longer collects before a capture (only under torch.compiler.config.force_cudagraph_gc), so
+    an automatic collection can start INSIDE one - any allocation of the captured Python code may trigger it - and run the
+    finalizers of dead objects of earlier work (captured graphs, events, streams' work) on the capturing thread, where
+    their HIP calls are not allowed: the process aborts in the middle of the collection.  The garbage is collected after
+    the capture instead.  (thread_local: other threads of the process, such as the RCCL watchdog polling its events, may
+    keep making HIP calls while this thread captures.)"""
+    enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            yield
+    finally:
+        if enabled:
+            gc.enable()
 
 
 def _req(t: torch.Tensor, dtype=None, name="tensor"):

@@ -360,7 +360,7 @@ class MultiTaskStep:
 
         def graph_of(fn, *a):
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            with ops.graph_capture(g):
                 if anchor is not None:
                     anchor.zero_()
                 fn(*a)
@@ -447,12 +447,10 @@ class MultiTaskStep:
             if self.linear_graphs:
                 self.graphs = self._capture_linear()
                 return True
-            # thread_local: other threads of the process (the RCCL watchdog of torch.distributed polls events)
-            # may keep making HIP calls while this thread captures
             graphs = []
             for j in range(len(self.block_ranges)):
                 gj = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gj, capture_error_mode="thread_local"):
+                with ops.graph_capture(gj):
                     self.part(j)
                 graphs.append(gj)
             self.graphs = graphs

@@ -232,16 +232,26 @@ class VisionTransformerMoE(nn.Module):
                  gate_dim=-1, moe_gate_type="noisy_vmoe", vmoe_noisy_std=1, gate_task_specific_dim=-1,
                  multi_gate=False, regu_experts_fromtask=False, num_experts_pertask=-1, num_tasks=-1,
                  gate_input_ahead=False, expert_prune=False, use_checkpointing=False, act_dtype=torch.float32,
-                 random_init=True, sem_force=False, convention="ckpt", fused="auto", **kwargs):
+                 random_init=True, sem_force=False, convention="ckpt", fused="auto", fused_grads="auto", **kwargs):
         """fused: "auto" (default) / True - forward(x, task_id) runs as ONE autograd node on the straight-line executor
         (m3vit_amd/fused.py: hipGraph replay, the parameters' .grad are views of its flat gradient buffer) whenever the call
         is one it covers, and through the per-op autograd Functions below otherwise (`fused_fallback_reason` says why);
-        False - always per-op.  The environment variable M3VIT_FUSED=0 forces False."""
+        False - always per-op.  The environment variable M3VIT_FUSED=0 forces False.
+        fused_grads: how that node delivers the parameter gradients.  "views" - the executor writes them into the .grad
+        views; no autograd node of a parameter runs, so parameter hooks, torch DDP's reducer and torch.autograd.grad do not
+        see them.  "autograd" - the parameters are inputs of the node and its backward returns their gradients (one flat
+        copy per backward call), so all of those work as on the per-op path.  "auto" (default) - "autograd" inside the
+        forward of a torch DistributedDataParallel that wraps this model or when a trainable parameter carries a tensor hook
+        or post-accumulate-grad hook, "views" otherwise.  `fused_grads_used` records what the last call used (None when it
+        did not run on the executor with autograd on)."""
         super().__init__()
         assert convention in ("ckpt", "origin")
+        assert fused_grads in ("auto", "views", "autograd"), f"fused_grads={fused_grads!r}: 'auto', 'views' or 'autograd'"
         self.convention = convention
         import os
         self.fused = False if os.environ.get("M3VIT_FUSED", "1") == "0" else fused
+        self.fused_grads = fused_grads
+        self.fused_grads_used = None
         self.use_checkpointing = bool(use_checkpointing)
         self.world_size = int(world_size)
         self._fused = None
@@ -322,11 +332,11 @@ class VisionTransformerMoE(nn.Module):
                 nn.init.constant_(m.bias, 0)
                 nn.init.constant_(m.weight, 1.0)
 
-    def _forward_fused(self, x, task_id):
+    def _forward_fused(self, x, task_id, grads):
         from .fused import FusedBackbone
         if self._fused is None:
             self._fused = FusedBackbone(self)
-        tok, cv = self._fused.forward(x, task_id)
+        tok, cv = self._fused.forward(x, task_id, grads or "views")
         if self.convention != "origin":
             return tok, cv
         # origin convention (origin/vision_transformer_moe.py:552-563): tokens only; the trainer sums the gates' stored
@@ -343,11 +353,14 @@ class VisionTransformerMoE(nn.Module):
         return tok
 
     def forward_features(self, x, gate_inp, task_id, sem):
+        self.fused_grads_used = None
         if self.fused:
             from .fused import FusedBackbone
-            self.fused_fallback_reason = FusedBackbone.unsupported(self, x, gate_inp, task_id, sem)
+            grads = FusedBackbone.grads_mode(self) if torch.is_grad_enabled() else None
+            self.fused_fallback_reason = FusedBackbone.unsupported(self, x, gate_inp, task_id, sem, grads or "views")
             if self.fused_fallback_reason is None:
-                return self._forward_fused(x, task_id)
+                self.fused_grads_used = grads
+                return self._forward_fused(x, task_id, grads)
             if self.fused is True:
                 raise RuntimeError(f"VisionTransformerMoE(fused=True): {self.fused_fallback_reason}")
         B = x.shape[0]
