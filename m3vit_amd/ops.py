@@ -54,14 +54,38 @@ def graph_capture(g: "torch.cuda.CUDAGraph"):
             gc.enable()
 
 
-def _req(t: torch.Tensor, dtype=None, name="tensor"):
+def _req(t: torch.Tensor, dtype=None, name="tensor", numel=None, min_numel=None):
+    """device, dtype, contiguity and size of a tensor handed to the C ABI, checked before anything is launched: the kernels
+    read and write raw pointers, so a wrong dtype is reinterpreted and an undersized buffer is written past its end.
+    numel: the exact element count the call reads / writes; min_numel: a lower bound (workspaces, index vectors)."""
+    if not isinstance(t, torch.Tensor):
+        raise _lib.M3Error(f"{name} must be a tensor, got {type(t).__name__}")
     if not t.is_cuda:
         raise _lib.M3Error(f"{name} must live on the GPU (no CPU path)")
     if dtype is not None and t.dtype != dtype:
         raise _lib.M3Error(f"{name} must be {dtype}, got {t.dtype}")
     if not t.is_contiguous():
         raise _lib.M3Error(f"{name} must be contiguous")
+    if numel is not None and t.numel() != numel:
+        raise _lib.M3Error(f"{name} must hold {numel} elements, got {t.numel()} (shape {tuple(t.shape)})")
+    if min_numel is not None and t.numel() < min_numel:
+        raise _lib.M3Error(f"{name} must hold at least {min_numel} elements, got {t.numel()}")
     return t
+
+
+def _act(t: torch.Tensor, name="tensor", numel=None):
+    """an activation-dtype tensor (fp32 / fp16 / bf16)"""
+    _req(t, name=name, numel=numel)
+    dt_code(t.dtype)
+    return t
+
+
+def _dims(t: torch.Tensor, n: int, name="tensor"):
+    if not isinstance(t, torch.Tensor):
+        raise _lib.M3Error(f"{name} must be a tensor, got {type(t).__name__}")
+    if t.dim() != n:
+        raise _lib.M3Error(f"{name} must be {n}-d, got shape {tuple(t.shape)}")
+    return t.shape
 
 
 # ----------------------------------------------------------------------------- gate
@@ -154,10 +178,17 @@ def gate_bwd_logits(noisy, idx, d_score, d_importance, k, *, balance_scale=1.0, 
 
 
 def gate_bwd_params(x, w_gate, d_logits, d_w_gate=None, beta_dw=0, dx=None, beta_dx=0, part_dw=None):
-    T, D = x.shape
-    E = w_gate.shape[1]
+    T, D = _dims(x, 2, "x")
+    E = _dims(w_gate, 2, "w_gate")[1]
+    _act(x, "x"); _req(w_gate, torch.float32, "w_gate", min_numel=D * E); _req(d_logits, torch.float32, "d_logits", T * E)
+    if d_w_gate is not None:
+        _req(d_w_gate, torch.float32, "d_w_gate", D * E)
+    if dx is not None:
+        _req(dx, torch.float32, "dx", T * D)
     if d_w_gate is not None and part_dw is None:
         part_dw = torch.empty((lib().m3_gate_dw_blocks(T), D, E), dtype=torch.float32, device=x.device)
+    if d_w_gate is not None:
+        _req(part_dw, torch.float32, "part_dw", min_numel=lib().m3_gate_dw_blocks(T) * D * E)
     check(lib().m3_gate_bwd_params(_p(x), dt_code(x.dtype), T, D, x.stride(0), _p(w_gate), E, _p(d_logits),
                                    _p(part_dw) if d_w_gate is not None else None, _p(d_w_gate), beta_dw,
                                    _p(dx), dx.stride(0) if dx is not None else 0, beta_dx, _stream()),
@@ -595,12 +626,14 @@ def colsum(dC, db, *, M=None, beta=0, c_row_idx=None, group_offsets=None, ws=Non
     _req(dC, name="dC"); _req(db, torch.float32, "db")
     G = 1 if db.dim() == 1 else db.shape[0]
     N = db.shape[-1]
+    if dC.dim() != 2 or dC.shape[1] != N:
+        raise _lib.M3Error(f"dC must be [M, {N}] like db's columns, got shape {tuple(dC.shape)}")
     if M is None:
         M = dC.shape[0]
     need = int(lib().m3_colsum_ws_elems(M, N, G))
     if ws is None:
         ws = torch.empty(need, dtype=torch.float32, device=dC.device)
-    assert ws.numel() >= need
+    _req(ws, torch.float32, "ws", min_numel=need)
     check(lib().m3_colsum(_p(dC), dt_code(dC.dtype), dC.stride(0), _p(c_row_idx), M, N, G, _p(group_offsets),
                           _p(ws), _p(db), beta, _stream()), "m3_colsum")
     return db
@@ -608,8 +641,11 @@ def colsum(dC, db, *, M=None, beta=0, c_row_idx=None, group_offsets=None, ws=Non
 
 # -------------------------------------------------------------------- combine / LN
 def combine_fwd(y, score, residual, out):
-    T, k = score.shape
+    T, k = _dims(score, 2, "score")
     D = y.shape[-1]
+    _req(score, torch.float32, "score"); _act(y, "y", T * k * D); _req(out, torch.float32, "out", T * D)
+    if residual is not None:
+        _req(residual, torch.float32, "residual", T * D)
     check(lib().m3_combine_fwd(_p(y), dt_code(y.dtype), _p(score), _p(residual), T, k, D, _p(out), _stream()),
           "m3_combine_fwd")
     return out
@@ -617,18 +653,26 @@ def combine_fwd(y, score, residual, out):
 
 def combine_bwd(dout, y, score, dy, dscore):
     """dy (may be None: d score only) [T*k, D] = score * dout ; dscore [T, k] = <dout, y>"""
-    T, k = score.shape
+    T, k = _dims(score, 2, "score")
     D = y.shape[-1]
+    _req(score, torch.float32, "score"); _act(y, "y", T * k * D); _req(dout, torch.float32, "dout", T * D)
+    _req(dscore, torch.float32, "dscore", T * k)
+    if dy is not None:
+        _req(dy, y.dtype, "dy", T * k * D)
     check(lib().m3_combine_bwd(_p(dout), _p(y), dt_code(y.dtype), _p(score), T, k, D, _p(dy), _p(dscore), _stream()),
           "m3_combine_bwd")
 
 
 def combine_gate_bwd(dxe, k, d_logits, w_gate, dh):
     """dh [T, D] (fp32 or dxe's dtype) = sum_j dxe[t*k+j] + d_logits [T, E] @ w_gate[:D] [D, E]^T  (one pass; m3_combine_gate_bwd)"""
-    T, E = d_logits.shape
+    T, E = _dims(d_logits, 2, "d_logits")
     D = dxe.shape[-1]
-    assert w_gate.dtype == torch.float32 and d_logits.dtype == torch.float32 and w_gate.is_contiguous()
-    assert tuple(w_gate.shape) == (D, E) and dxe.shape[0] == T * k and tuple(dh.shape) == (T, D) and dh.is_contiguous()
+    _req(d_logits, torch.float32, "d_logits"); _req(w_gate, torch.float32, "w_gate", D * E); _act(dxe, "dxe", T * k * D)
+    _act(dh, "dh", T * D)
+    if tuple(w_gate.shape) != (D, E):
+        raise _lib.M3Error(f"w_gate must be [{D}, {E}], got {tuple(w_gate.shape)}")
+    if dh.dtype not in (torch.float32, dxe.dtype):
+        raise _lib.M3Error(f"dh must be float32 or {dxe.dtype}, got {dh.dtype}")
     check(lib().m3_combine_gate_bwd(_p(dxe), dt_code(dxe.dtype), T, k, D, _p(d_logits), _p(w_gate), E, _p(dh), dt_code(dh.dtype),
                                     _stream()), "m3_combine_gate_bwd")
     return dh
@@ -636,13 +680,18 @@ def combine_gate_bwd(dxe, k, d_logits, w_gate, dh):
 
 def gather_rows(src, idx, dst, div=1, k=1):
     """dst[i] = sum_{j<k} src[idx[i*k+j] // div]."""
-    nout, D = dst.shape
+    nout, D = _dims(dst, 2, "dst")
+    _act(dst, "dst"); _req(src, dst.dtype, "src"); _req(idx, torch.int32, "idx", min_numel=nout * k)
+    if src.numel() % max(D, 1) or (src.dim() > 0 and src.shape[-1] != D):
+        raise _lib.M3Error(f"src rows must be {D} wide like dst, got shape {tuple(src.shape)}")
     check(lib().m3_gather_rows(_p(src), dt_code(src.dtype), _p(idx), div, nout, k, D, _p(dst), _stream()), "m3_gather_rows")
     return dst
 
 
 def layernorm_fwd(x, gamma, beta, y, mean, rstd, eps=1e-6):
-    T, D = x.shape
+    T, D = _dims(x, 2, "x")
+    _req(x, torch.float32, "x"); _req(gamma, torch.float32, "gamma", D); _req(beta, torch.float32, "beta", D)
+    _act(y, "y", T * D); _req(mean, torch.float32, "mean", T); _req(rstd, torch.float32, "rstd", T)
     check(lib().m3_layernorm_fwd(_p(x), T, D, _p(gamma), _p(beta), float(eps), _p(y), dt_code(y.dtype), _p(mean),
                                  _p(rstd), _stream()), "m3_layernorm_fwd")
 
@@ -650,10 +699,22 @@ def layernorm_fwd(x, gamma, beta, y, mean, rstd, eps=1e-6):
 def layernorm_bwd(dy, x, mean, rstd, gamma, dx_res, dx, dgamma, dbeta, beta=0, ws=None, dx_act=None):
     """dgamma = dbeta = None: the parameter-gradient partials stay in ws (fp32 [2, ln_bwd_blocks(T), D]) for a later
     batched layernorm_bwd_reduce."""
-    T, D = x.shape
+    T, D = _dims(x, 2, "x")
     nblk = lib().m3_ln_bwd_blocks(T, D)
+    _req(x, torch.float32, "x"); _act(dy, "dy", T * D); _req(mean, torch.float32, "mean", T)
+    _req(rstd, torch.float32, "rstd", T); _req(gamma, torch.float32, "gamma", D); _req(dx, torch.float32, "dx", T * D)
+    if dx_res is not None:
+        _req(dx_res, torch.float32, "dx_res", T * D)
+    for t_, n_ in ((dgamma, "dgamma"), (dbeta, "dbeta")):
+        if t_ is not None:
+            _req(t_, torch.float32, n_, D)
+    if (dgamma is None) != (dbeta is None):
+        raise _lib.M3Error("layernorm_bwd: dgamma and dbeta go together (both None: the partials stay in ws)")
+    if dx_act is not None:
+        _act(dx_act, "dx_act", T * D)
     if ws is None:
         ws = torch.empty(2 * nblk * D, dtype=torch.float32, device=x.device)
+    _req(ws, torch.float32, "ws", min_numel=2 * nblk * D)
     check(lib().m3_layernorm_bwd(_p(dy), dt_code(dy.dtype), _p(x), _p(mean), _p(rstd), _p(gamma), _p(dx_res), T, D,
                                  _p(dx), _p(ws), _p(dgamma), _p(dbeta), beta, _p(dx_act),
                                  dt_code(dx_act.dtype) if dx_act is not None else M3_F32, _stream()), "m3_layernorm_bwd")
@@ -675,21 +736,31 @@ class LnGradTable:
 def layernorm_bwd_reduce(ws, nblk, D, table: LnGradTable, first, count, beta=1):
     """dgamma / dbeta of LayerNorms first .. first+count-1 from their partial slots ws[j] (fp32 [n, 2, nblk, D])"""
     _req(ws, torch.float32, "ws")
-    assert ws.dim() == 4 and ws.shape[1] == 2 and ws.shape[2] == nblk and ws.shape[3] == D and first + count <= table.n
+    if ws.dim() != 4 or tuple(ws.shape[1:]) != (2, nblk, D):
+        raise _lib.M3Error(f"ws must be [n, 2, {nblk}, {D}], got {tuple(ws.shape)}")
+    if first < 0 or count < 0 or first + count > min(table.n, ws.shape[0]):
+        raise _lib.M3Error(f"layers [{first}, {first + count}) exceed the table ({table.n}) or the workspace ({ws.shape[0]})")
     check(lib().m3_layernorm_bwd_reduce(_p(ws), ws.stride(0), nblk, D, _p(table.table), first, count, beta, _stream()),
           "m3_layernorm_bwd_reduce")
 
 
 # ------------------------------------------------------------------------ attention
 def attention_fwd(qkv, B, N, heads, dh, o, lse):
+    _act(qkv, "qkv", B * N * 3 * heads * dh); _req(o, qkv.dtype, "o", B * N * heads * dh)
+    _req(lse, torch.float32, "lse", B * heads * N)
     check(lib().m3_attention_fwd(_p(qkv), dt_code(qkv.dtype), B, N, heads, dh, _p(o), _p(lse), _stream()),
           "m3_attention_fwd")
 
 
 def attention_bwd(qkv, o, d_o, lse, B, N, heads, dh, dqkv, dq_ws=None):
     need = int(lib().m3_attention_bwd_ws_elems(B, N, heads, dh))
+    C = heads * dh
+    _act(qkv, "qkv", B * N * 3 * C); _req(o, qkv.dtype, "o", B * N * C); _req(d_o, qkv.dtype, "d_o", B * N * C)
+    _req(lse, torch.float32, "lse", B * heads * N); _req(dqkv, qkv.dtype, "dqkv", B * N * 3 * C)
     if need and dq_ws is None:
         dq_ws = torch.empty(need, dtype=torch.float32, device=qkv.device)
+    if need:
+        _req(dq_ws, torch.float32, "dq_ws", min_numel=need)
     check(lib().m3_attention_bwd(_p(qkv), _p(o), _p(d_o), _p(lse), dt_code(qkv.dtype), B, N, heads, dh, _p(dqkv),
                                  _p(dq_ws) if need else None, _stream()), "m3_attention_bwd")
 
@@ -697,8 +768,11 @@ def attention_bwd(qkv, o, d_o, lse, B, N, heads, dh, dqkv, dq_ws=None):
 # ---------------------------------------------------------------------- elementwise
 def cast_matrix(src, dst, transpose=False):
     """src f32 [G,R,C] or [R,C] -> dst (act dtype) same shape, or [G,C,R] when transpose."""
+    if src.dim() not in (2, 3):
+        raise _lib.M3Error(f"src must be [G,R,C] or [R,C], got shape {tuple(src.shape)}")
     G = 1 if src.dim() == 2 else src.shape[0]
     R, C = src.shape[-2], src.shape[-1]
+    _req(src, torch.float32, "src"); _act(dst, "dst", G * R * C)
     check(lib().m3_cast_matrix(_p(src), G, R, C, 1 if transpose else 0, _p(dst), dt_code(dst.dtype), _stream()),
           "m3_cast_matrix")
     return dst
@@ -738,22 +812,24 @@ class CastPlan:
 
 def add_f32(dst, src):
     """dst += src (flat fp32 buffers)."""
-    _req(dst, torch.float32, "dst"); _req(src, torch.float32, "src")
-    assert dst.numel() == src.numel()
+    _req(dst, torch.float32, "dst"); _req(src, torch.float32, "src", dst.numel())
     check(lib().m3_add_f32(_p(dst), _p(src), dst.numel(), _stream()), "m3_add_f32")
     return dst
 
 
 def cast_f32(src, dst):
+    _req(src, torch.float32, "src"); _act(dst, "dst", src.numel())
     check(lib().m3_cast_f32(_p(src), src.numel(), _p(dst), dt_code(dst.dtype), _stream()), "m3_cast_f32")
     return dst
 
 
 def scale_rows_cast(src, row_scale, div, dst):
     """dst[r, :] = row_scale[r // div] * src[r, :] (src fp32 [rows, cols], dst fp32 / f16)"""
-    _req(src, torch.float32, "src"); _req(row_scale, torch.float32, "row_scale"); _req(dst, name="dst")
-    rows, cols = src.shape
-    assert row_scale.numel() * div >= rows
+    rows, cols = _dims(src, 2, "src")
+    _req(src, torch.float32, "src"); _act(dst, "dst", rows * cols)
+    if div < 1:
+        raise _lib.M3Error(f"div must be >= 1, got {div}")
+    _req(row_scale, torch.float32, "row_scale", min_numel=-(-rows // div))
     check(lib().m3_scale_rows_cast(_p(src), rows, cols, _p(row_scale), div, _p(dst), dt_code(dst.dtype), _stream()),
           "m3_scale_rows_cast")
     return dst
@@ -781,7 +857,9 @@ def relu_up2x_fwd(x, relu=True, out_dtype=None):
 def relu_up2x_bwd(dy, x, relu=True):
     _nhwc(dy, "dy"); _nhwc(x, "x")
     N, C, H, W = x.shape
-    assert tuple(dy.shape) == (N, C, 2 * H, 2 * W)
+    if tuple(dy.shape) != (N, C, 2 * H, 2 * W):
+        raise _lib.M3Error(f"dy must be [{N}, {C}, {2 * H}, {2 * W}], got {tuple(dy.shape)}")
+    dt_code(dy.dtype)
     dx = torch.empty_like(x, memory_format=torch.channels_last)
     check(lib().m3_relu_up2x_bwd(_p(dy), dt_code(dy.dtype), _p(x), dt_code(x.dtype), N, H, W, C, 1 if relu else 0, _p(dx),
                                  _stream()), "m3_relu_up2x_bwd")
@@ -789,16 +867,25 @@ def relu_up2x_bwd(dy, x, relu=True):
 
 
 def im2row(img, P, rows):
-    B, Cin, H, W = img.shape
+    B, Cin, H, W = _dims(img, 4, "img")
+    if P < 1 or H % P or W % P:
+        raise _lib.M3Error(f"im2row: H, W ({H}, {W}) must be multiples of the patch size {P}")
+    _req(img, torch.float32, "img"); _act(rows, "rows", B * (H // P) * (W // P) * Cin * P * P)
     check(lib().m3_im2row(_p(img), B, Cin, H, W, P, _p(rows), dt_code(rows.dtype), _stream()), "m3_im2row")
     return rows
 
 
 def assemble_tokens(patch, cls, pos, B, np_, D, tokens):
+    _req(patch, torch.float32, "patch", B * np_ * D); _req(cls, torch.float32, "cls", D)
+    _req(pos, torch.float32, "pos", (np_ + 1) * D); _req(tokens, torch.float32, "tokens", B * (np_ + 1) * D)
     check(lib().m3_assemble_tokens(_p(patch), _p(cls), _p(pos), B, np_, D, _p(tokens), _stream()), "m3_assemble_tokens")
     return tokens
 
 
 def tokens_bwd(dtok, B, np_, D, dpatch, dpos, dcls, beta=0):
+    _req(dtok, torch.float32, "dtok", B * (np_ + 1) * D); _req(dpos, torch.float32, "dpos", (np_ + 1) * D)
+    _req(dcls, torch.float32, "dcls", D)
+    if dpatch is not None:
+        _act(dpatch, "dpatch", B * np_ * D)
     check(lib().m3_tokens_bwd(_p(dtok), B, np_, D, _p(dpatch), dt_code(dpatch.dtype) if dpatch is not None else M3_F32,
                               _p(dpos), _p(dcls), beta, _stream()), "m3_tokens_bwd")

@@ -679,7 +679,7 @@ def test_combine_gate_bwd_sums_the_routed_rows_and_adds_the_gate_share(ops, dtyp
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("D", [384, 768, 192])
+@pytest.mark.parametrize("D", [384, 768, 192, 132, 260, 516, 1024])
 def test_layernorm_fwd_bwd(ops, dtype, D):
     T = 517
     x = rnd(T, D, seed=61) * 2 + 0.3
