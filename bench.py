@@ -2,7 +2,7 @@
 """Headline benchmark: images/sec, forward+backward, ViT-S/16 + MoE (E=16, top-k=4, multi-gate),
 224x224, batch 128 per GPU (BASELINE.json configs[1]), synthetic data, random-init weights.
 
-    python bench.py --gpus N --steps K --warmup W [--dtype f16|f32] [--batch 128] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dtype f16|f32] [--batch 128] [--dump-outputs DIR] [--full]
 
 One "step" = what one reference training iteration does to the backbone for one batch
 (train/train_utils.py:423-457, multi_gate joint path; models/models.py:299-301): refresh the
@@ -11,8 +11,13 @@ gate) and one full backward (d tokens + 0.01 * cv_loss), gradients accumulated; 
 experts are sharded E/N per rank (expert parallel: all-to-all of the routed rows over RCCL, dense gradients
 all-reduced; utils/common_config.py:179-185) - the primary value when E % N == 0 - and the replicated-experts
 data-parallel form (the reference's --moe_data_distributed mode, :179-181) is timed too (sub-objects "ep" / "dp").
-At N = 1 the fp32 run (train_fastmoe.py's arithmetic) follows the fp16 one as the sub-object "f32".  Decoder heads / losses are out
-of scope: d tokens is a fixed synthetic tensor.
+Decoder heads / losses are out of scope: d tokens is a fixed synthetic tensor.
+
+A plain N = 1 run times the headline configuration only: set-up, W warm-up steps, K timed steps, the
+--dump-outputs arrays if asked for, the line.  --full adds what needs runs of its own: the roofline object
+(instrumented extra steps), the shared-stem schedule, the fp32 run ("f32"), the skewed routing ("skew"), the
+ViT-Base configurations ("configs3" / "configs4"), the drop-in module path ("module_path") and the CPU baseline.
+At N > 1 every leg is a candidate for the headline, so a plain run times them all and --full adds nothing.
 
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field definitions).
 """
@@ -41,7 +46,7 @@ CV_WEIGHT = 0.01                           # --moe_noisy_gate_loss_weight defaul
 # The workloads a line can be quoted on.  configs[1] is BASELINE.json's metric configuration (the default and the driver's line);
 # configs[3] / configs[4] are the ViT-Base configurations in their single-GPU form (all experts local):
 # the regime where the expert grouped GEMMs contract over K = 768 / 3072 and the MFMA roof, not operand delivery, is the bound.
-# They are timed in the default run as the sub-objects "configs3" / "configs4" (own roofline), or alone with --config 3 / 4.
+# They are timed in a --full run as the sub-objects "configs3" / "configs4" (own roofline), or alone with --config 3 / 4.
 WORKLOADS = {
     1: dict(name="configs[1]: ViT-Small/16 + MoE E=16 top-k=4 multi_gate, synthetic 224x224", batch=128,
             cfg=dict(img_size=(224, 224), embed_dim=384, depth=12, num_heads=12, mlp_ratio=4.0, moe_mlp_ratio=1.0,
@@ -66,11 +71,15 @@ def parse():
     ap.add_argument("--batch", type=int, default=None, help="images per GPU and step (default: the workload's own - 128, 128, 8)")
     ap.add_argument("--config", type=int, choices=sorted(WORKLOADS), default=1, help="which BASELINE.json configuration the line is "
                     "quoted on: 1 = the metric's (default); 3 / 4 = the ViT-Base configurations, single-GPU form (N = 1 only)")
-    ap.add_argument("--no-vitb", action="store_true", help="N = 1, --config 1: skip the configs[3] / configs[4] sub-objects")
-    ap.add_argument("--no-skew", action="store_true", help="N = 1, --config 1: skip the skewed-routing sub-object \"skew\"")
+    ap.add_argument("--full", action="store_true", help="N = 1: beside the headline also time and report what takes runs of its "
+                    "own - the roofline object, the shared-stem schedule, the fp32 run, the skewed routing, the ViT-Base "
+                    "configurations, the drop-in module path, the CPU baseline (each --no-* flag below drops one of them); "
+                    "a plain run does only the headline's set-up, warm-up and timed steps")
+    ap.add_argument("--no-vitb", action="store_true", help="--full, N = 1, --config 1: skip the configs[3] / configs[4] sub-objects")
+    ap.add_argument("--no-skew", action="store_true", help="--full, N = 1, --config 1: skip the skewed-routing sub-object \"skew\"")
     ap.add_argument("--checkpoint", action="store_true",
                     help="the reference's default memory mode: keep block inputs only, recompute each block in backward")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full, N = 1: skip the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=4)
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured hipGraph")
     ap.add_argument("--noisy", action="store_true", help="variant: noisy-gate training (vmoe_noisy_std = 1, caller-supplied noise, CDF load loss)")
@@ -87,8 +96,8 @@ def parse():
     ap.add_argument("--share-stem", action="store_true", help="make the shared-stem schedule the primary figure: the "
                     "task-independent stem (patch embedding + the blocks below the first MoE block) computed once per step for "
                     "all task passes instead of once per pass (MultiTaskStep share_stem: same gradients).  Without the flag "
-                    "`value` is the reference's schedule - one FULL pass per task - and the shared-stem step is timed as well and "
-                    "reported as the sub-object \"shared_stem\"")
+                    "`value` is the reference's schedule - one FULL pass per task - and a --full run times the shared-stem step "
+                    "as well and reports it as the sub-object \"shared_stem\"")
     ap.add_argument("--no-share-stem", action="store_true", help="do not time the shared-stem schedule at all")
     ap.add_argument("--ep", action="store_true", help="N > 1: time ONLY the expert-parallel form (experts sharded over the "
                     "ranks, all-to-all over RCCL); default: expert parallel (primary, when E %% N == 0) AND data parallel")
@@ -104,11 +113,11 @@ def parse():
                     "of torch.distributed, with --ep-chunks chunks.  Opt-in: those entry points have only ever run on a one-rank "
                     "communicator (the build box has one GPU)")
     ap.add_argument("--dp-only", action="store_true", help="N > 1: time only the replicated-experts data-parallel form")
-    ap.add_argument("--no-f32", action="store_true", help="N = 1: skip the fp32 run reported as the sub-object \"f32\"")
+    ap.add_argument("--no-f32", action="store_true", help="--full, N = 1: skip the fp32 run reported as the sub-object \"f32\"")
     ap.add_argument("--module-path", action="store_true", help="N = 1: time ONLY the drop-in module path (install_fmoe_shim() + "
                     "m3vit_amd.vit.VisionTransformerMoE + torch.autograd: backbone(x, task_id) per task, one loss.backward()) and "
-                    "report it as `value`; by default it is timed after the executor and reported as the sub-object \"module_path\"")
-    ap.add_argument("--no-module-path", action="store_true", help="N = 1: do not time the drop-in module path")
+                    "report it as `value`; a --full run times it after the executor and reports it as the sub-object \"module_path\"")
+    ap.add_argument("--no-module-path", action="store_true", help="--full, N = 1: do not time the drop-in module path")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="N = 1: after the timed steps of the primary "
                     "configuration, write what its last step computed - the gradient of every parameter, fp32 - as "
                     f"DIR/grad.<parameter name>.npy (a parameter of more than {DUMP_MAX_ELEMS} elements as a fixed, seeded "
@@ -470,8 +479,9 @@ def main():
         return roofline
 
     # ---- which configurations this invocation times
-    #  N = 1: the primary dtype (f16, the reference's AMP arithmetic) with the roofline object, then - unless --dtype
-    #         was given explicitly - the fp32 run (the arithmetic of train_fastmoe.py) as the sub-object "f32";
+    #  N = 1: the primary dtype (f16, the reference's AMP arithmetic) and nothing else; with --full also its roofline
+    #         object, then (primary f16) the fp32 run (the arithmetic of train_fastmoe.py) as the sub-object "f32" and
+    #         the other sub-objects and the CPU baseline;
     #  N > 1: north_star's expert-parallel form (experts sharded E/N per rank, all-to-all over RCCL) is the primary
     #         when the experts divide over the ranks, and the replicated-experts data-parallel form (the reference's
     #         --moe_data_distributed mode) is timed as well: both appear as the sub-objects "ep" and "dp".
@@ -496,13 +506,13 @@ def main():
                        "activation_checkpointing": main_res["activation_checkpointing"],
                        "shared_stem": main_res["shared_stem"],
                        "peak_hbm_gib": main_res["peak_hbm_gib"],
-                       "parallelism": main_res["parallelism"]},
+                       "parallelism": main_res["parallelism"], "full": bool(args.full)},
             "model_tflops": main_res["model_tflops"],
         }
         if "roofline" in main_res:
             out["roofline"] = main_res["roofline"]
         out.update(extra)
-        if final and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if final and rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 cores = len(os.sched_getaffinity(0))
             except AttributeError:
@@ -565,14 +575,14 @@ def main():
         # `value` is the reference's schedule: one FULL backbone pass per task.  Every task pass of a step reads the same images
         # (train/train_utils.py:248-256) and the patch embedding + block 0 see neither task id nor gate, so they can be computed
         # once per step with their backward on the summed d x (m3vit_amd/step.py share_stem; identical gradients:
-        # tests/test_engine.py::test_shared_stem_step_matches_per_task_stems) - 23 instead of 24 block passes.  That step is
-        # timed too and reported BESIDE the headline as "shared_stem" (or as the headline with --share-stem, then with the
+        # tests/test_engine.py::test_shared_stem_step_matches_per_task_stems) - 23 instead of 24 block passes.  With --full that
+        # step is timed too and reported BESIDE the headline as "shared_stem" (or as the headline with --share-stem, then with the
         # reference's schedule beside it as "per_task_stems").
         base1 = args.config == 1          # shared stem, fp32, module path and the sub-objects below belong to the metric's configuration
         can_share = not args.serial_tasks and not args.no_share_stem and base1
         share = bool(args.share_stem) and can_share
-        main_res = run_mode(args.dtype, False, True, share_stem=share, dump_dir=args.dump_outputs)
-        if can_share:
+        main_res = run_mode(args.dtype, False, args.full, share_stem=share, dump_dir=args.dump_outputs)
+        if can_share and args.full:
             other = "per_task_stems" if share else "shared_stem"
             ot = attempt(other, lambda: run_mode(args.dtype, False, False, share_stem=not share))
             if ot is not None:
@@ -582,14 +592,14 @@ def main():
                                          "patch embedding + block 0 computed once per step for both task passes, their backward once on "
                                          "the summed d x: same gradients, 23 instead of 24 block passes (model_tflops counts the FLOPs "
                                          "executed)")}
-        if args.dtype == "f16" and not args.no_f32 and base1:
+        if args.full and args.dtype == "f16" and not args.no_f32 and base1:
             f32 = attempt("f32", lambda: run_mode("f32", False, True, share_stem=share))
             if f32 is not None:
                 extra["f32"] = {k: f32[k] for k in ("value", "ms_per_step", "model_tflops", "launch", "roofline")}
                 extra["f32"]["dtype"] = "f32"
-        plain = base1 and not args.serial_tasks and not args.checkpoint and not (args.noisy or args.skew) and not args.no_graph
+        side_legs = args.full and base1 and not args.serial_tasks and not args.checkpoint and not (args.noisy or args.skew) and not args.no_graph
         sub_steps, sub_warm = min(args.steps, 20), min(args.warmup, 5)
-        if plain and not args.no_skew and args.batch == WORKLOADS[1]["batch"]:
+        if side_legs and not args.no_skew and args.batch == WORKLOADS[1]["batch"]:
             # routing-skew variant beside the headline: +8 on expert 0's gate logit puts it into EVERY token's top-k
             # (4x the mean load) - what the device-side load balancing of the grouped weight gradients and the tile prefix of the
             # grouped GEMMs are for; same work, same FLOPs, only the distribution over the experts changes
@@ -598,7 +608,7 @@ def main():
                 extra["skew"] = {"value": sk["value"], "ms_per_step": sk["ms_per_step"], "steps": sk["steps"], "warmup": sk["warmup"],
                                  "ratio_to_value": round(sk["value"] / main_res["value"], 4),
                                  "routing": "expert 0 in every token's top-k (4x the mean load), the other three picks as routed"}
-        if plain and not args.no_vitb and args.dtype in ("f16", "bf16"):
+        if side_legs and not args.no_vitb and args.dtype in ("f16", "bf16"):
             # the ViT-Base configurations, single-GPU form: the expert grouped GEMMs contract over K = 768 / 3072 there
             for w in (3, 4):
                 vb = attempt(f"configs{w}", lambda w=w: run_mode(args.dtype, False, True, workload=w, skew=False, steps=sub_steps,
@@ -608,7 +618,7 @@ def main():
                                                                "task_passes", "tokens_per_image", "steps", "warmup",
                                                                "peak_hbm_gib", "roofline")}
                     extra[f"configs{w}"]["unit"] = "images/s"
-        if not args.no_module_path and plain:
+        if not args.no_module_path and side_legs:
             # The number above is the executor driven directly (m3vit_amd.step.MultiTaskStep).  What a maintainer who drops
             # the library in calls is the MODULE API - install_fmoe_shim() + VisionTransformerMoE.forward(x, task_id) per task +
             # one loss.backward() (models/models.py:299-320, train/train_utils.py:423-457): timed here on the same

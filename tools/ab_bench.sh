@@ -4,7 +4,7 @@
 A=$1; B=$2; R=${3:-3}; shift 3 || true
 for r in $(seq 1 $R); do
   for L in "$A" "$B"; do
-    ms=$(M3VIT_LIB=$L timeout -k 10 300 python bench.py --no-f32 --no-cpu-baseline --steps 20 --warmup 5 "$@" 2>/dev/null | python -c "import sys,json; print(json.loads(sys.stdin.read())['ms_per_step'])")
+    ms=$(M3VIT_LIB=$L timeout -k 10 300 python bench.py --steps 20 --warmup 5 "$@" 2>/dev/null | python -c "import sys,json; print(json.loads(sys.stdin.read())['ms_per_step'])")
     echo "round $r  $L  $ms ms/step"
   done
 done

@@ -6,7 +6,7 @@
 A=$1; B=$2; R=${3:-3}; shift 3 || true
 for r in $(seq 1 $R); do
   for T in "$A" "$B"; do
-    ms=$(cd $T && timeout -k 10 300 python bench.py --no-f32 --no-cpu-baseline --steps 20 --warmup 5 "$@" 2>/dev/null | python -c "import sys,json; print(json.loads(sys.stdin.read())['ms_per_step'])")
+    ms=$(cd $T && timeout -k 10 300 python bench.py --steps 20 --warmup 5 "$@" 2>/dev/null | python -c "import sys,json; print(json.loads(sys.stdin.read())['ms_per_step'])")
     echo "round $r  $T  $ms ms/step"
   done
 done

@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 C=$1; O=$R/$2; HEAD=${3:-unknown}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="--config $C --no-f32 --no-cpu-baseline --no-vitb --no-skew --no-module-path --steps 2 --warmup 1 --serial-tasks --no-graph"
+B="--config $C --full --no-f32 --no-cpu-baseline --no-vitb --no-skew --no-module-path --steps 2 --warmup 1 --serial-tasks --no-graph"
 rm -rf /tmp/pf_$C /tmp/pw_$C
 timeout -k 10 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/pf_$C -o run -- python $R/bench.py $B > $O/fetch_cfg$C.log 2>&1
 timeout -k 10 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d /tmp/pw_$C -o run -- python $R/bench.py $B > $O/write_cfg$C.log 2>&1

@@ -9,12 +9,12 @@ HEAD=${1:-unknown}
 O=$R/gpurun_out/final
 rm -rf $O; mkdir -p $O
 cd $R
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err
-B="--no-f32 --no-cpu-baseline --no-vitb --no-skew --no-module-path"
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err
+B="--full --no-f32 --no-cpu-baseline --no-vitb --no-skew --no-module-path"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof2 -o run -- python $R/bench.py --steps 8 --warmup 2 $B > $O/prof2.json 2> $O/prof2.err
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof1 -o run -- python $R/bench.py --steps 8 --warmup 2 $B --serial-tasks --no-graph > $O/prof1.json 2> $O/prof1.err
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof1f32 -o run -- python $R/bench.py --dtype f32 --steps 4 --warmup 1 --no-cpu-baseline --no-vitb --no-skew --no-module-path --serial-tasks --no-graph > $O/prof1_f32.json 2> $O/prof1_f32.err
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof1f32 -o run -- python $R/bench.py --dtype f32 --steps 4 --warmup 1 --full --no-cpu-baseline --no-vitb --no-skew --no-module-path --serial-tasks --no-graph > $O/prof1_f32.json 2> $O/prof1_f32.err
 cp $(find $O/prof2 -name "*kernel_stats.csv" | head -1) $O/kernel_stats_two_streams.csv
 cp $(find $O/prof1 -name "*kernel_stats.csv" | head -1) $O/kernel_stats_serial.csv
 cp $(find $O/prof1f32 -name "*kernel_stats.csv" | head -1) $O/kernel_stats_serial_f32.csv

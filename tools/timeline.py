@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Concurrency of the two-stream step from a rocprofv3 kernel trace (rocpd database): per step-sized window, how long
 0 / 1 / >= 2 kernels were in flight, and which kernels run while nothing else does.
-    rocprofv3 --kernel-trace -d out -o run -- python bench.py --steps 8 --warmup 2 --no-f32 --no-cpu-baseline
+    rocprofv3 --kernel-trace -d out -o run -- python bench.py --steps 8 --warmup 2
     python tools/timeline.py out/.../run_results.db"""
 import sqlite3
 import sys
