@@ -836,6 +836,9 @@ extern "C" int m3_gate_bwd_params(const void *x, int x_dtype, int64_t T, int D, 
   M3_REQUIRE(dtype_ok(x_dtype), "m3_gate_bwd_params: bad dtype");
   M3_REQUIRE(E >= 2 && E <= 64 && D > 0 && D <= 1024, "m3_gate_bwd_params: E in [2,64], D <= 1024");
   M3_REQUIRE((d_w_gate == nullptr) == (part_dw == nullptr), "m3_gate_bwd_params: part_dw and d_w_gate go together");
+  // checked before anything is launched: a rejected dx must not leave d_w_gate half updated
+  M3_REQUIRE(!dx || (size_t)D * E * sizeof(float) <= 64 * 1024, "m3_gate_bwd_params: D*E too large for the dx kernel");
+  M3_REQUIRE(!dx || lddx >= D, "m3_gate_bwd_params: lddx < D");
   if (T == 0) return M3_OK;
   hipStream_t s = (hipStream_t)stream;
   const int es = dtype_size(x_dtype);
@@ -890,7 +893,6 @@ extern "C" int m3_gate_bwd_params(const void *x, int x_dtype, int64_t T, int D, 
   }
   if (dx) {
     const size_t lds = (size_t)D * E * sizeof(float);
-    M3_REQUIRE(lds <= 64 * 1024, "m3_gate_bwd_params: D*E too large for the dx kernel");
     int64_t blocks = (T + 3) / 4;
     if (blocks > 2048) blocks = 2048;
     const dim3 grid((unsigned)blocks), block(256);

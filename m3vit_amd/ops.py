@@ -101,10 +101,10 @@ def gate_fwd(x, w_gate, k, logit_bias=None, noise=None, noise_std=0.0, dense=Tru
     route: also build the dispatch metadata (result["route"]: a Route as route_build(idx32, E) returns it) from the gate
     kernel's own per-block counts - the histogram pass is not launched and the scan rides in the balance launch
     (m3_balance_route); needs k | 16."""
-    _req(x, name="x"); _req(w_gate, torch.float32, "w_gate")
-    T, D = x.shape
-    E = w_gate.shape[1]
-    assert w_gate.shape[0] == D
+    _req(x, name="x")
+    T, D = _dims(x, 2, "x")
+    E = _dims(w_gate, 2, "w_gate")[1]
+    _req(w_gate, torch.float32, "w_gate", D * E)
     dev = x.device
     kp = min(k + 1, E)
     f32 = torch.float32
@@ -127,9 +127,11 @@ def gate_fwd(x, w_gate, k, logit_bias=None, noise=None, noise_std=0.0, dense=Tru
     load = torch.empty(E, dtype=torch.int64, device=dev)
     loss = torch.empty((), dtype=f32, device=dev)
     if logit_bias is not None:
-        _req(logit_bias, f32, "logit_bias")
+        _req(logit_bias, f32, "logit_bias", E)
     if noise is not None:
-        _req(noise, f32, "noise")
+        _req(noise, f32, "noise", T * E)
+    if loss_acc is not None:
+        _req(loss_acc, f32, "loss_acc", 1)
     route = bool(route) and T > 0 and 16 % k == 0 and want_idx32
     pc = torch.empty((2, max(nblk, 1), E), dtype=torch.int32, device=dev) if route else None     # counts, then their prefix
     a = _lib.GateFwdArgs(_p(x), dt_code(x.dtype), T, D, x.stride(0), _p(w_gate), E, _p(logit_bias), _p(noise),
@@ -166,10 +168,21 @@ def gate_bwd_logits(noisy, idx, d_score, d_importance, k, *, balance_scale=1.0, 
     """d_logits [T,E] from d_score [T,k], d_top [T,k+1], balance_scale * (d_importance, d_load_prob) [E].
     balance_scale_dev: optional 1-element f32 device tensor multiplied onto balance_scale inside the kernel.
     out_act: optional [T,E] tensor (activation dtype) that receives a second copy of the result."""
-    T, E = noisy.shape
+    T, E = _dims(noisy, 2, "noisy")
+    kp = min(k + 1, E)
+    f32 = torch.float32
+    _req(noisy, f32, "noisy")
+    _req(idx, torch.int64, "idx", T * k)
+    for t_, name, n in ((clean, "clean", T * E), (out, "out", T * E), (d_score, "d_score", T * k),
+                        (d_top, "d_top", T * kp), (top_logits, "top_logits", T * kp), (d_importance, "d_importance", E),
+                        (d_load_prob, "d_load_prob", E), (balance_scale_dev, "balance_scale_dev", 1)):
+        if t_ is not None:
+            _req(t_, f32, name, n)
+    if idx_next is not None:
+        _req(idx_next, torch.int32, "idx_next", T)
+    if out_act is not None:
+        _act(out_act, "out_act", T * E)
     dl = torch.empty_like(noisy) if out is None else out
-    if balance_scale_dev is not None:
-        _req(balance_scale_dev, torch.float32, "balance_scale_dev")
     a = _lib.GateBwdArgs(_p(noisy), _p(clean), _p(top_logits), _p(idx), _p(idx_next), _p(d_score), _p(d_top),
                          _p(d_importance), _p(d_load_prob), float(balance_scale), float(noise_std), T, E, k, _p(dl),
                          _p(balance_scale_dev), _p(out_act), dt_code(out_act.dtype) if out_act is not None else M3_F32)
@@ -241,7 +254,8 @@ class EpPlan:
 def ep_plan(send_counts64, recv_counts64, world: int, e_loc: int, regroup_buf: torch.Tensor, splits_host=None) -> EpPlan:
     """Plan of one expert-parallel exchange from the two count vectors, computed on the device; the host reads only the
     2 * world split sizes (one small copy into pinned memory; torch.distributed's a2a-v takes python lists)."""
-    _req(send_counts64, torch.int64, "send_counts"); _req(recv_counts64, torch.int64, "recv_counts")
+    _req(send_counts64, torch.int64, "send_counts", world * e_loc)
+    _req(recv_counts64, torch.int64, "recv_counts", world * e_loc)
     _req(regroup_buf, torch.int32, "regroup_buf")
     dev = send_counts64.device
     p = EpPlan()

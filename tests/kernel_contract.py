@@ -9,6 +9,7 @@
 * assert_within(out, ref64, bound64) - the elementwise check |out - ref| <= bound, NaN counting as a failure.
 * the error-bound builders, one per kernel family (derivations next to each).
 * snapshot() / unchanged() - the inputs of a call keep their bits.
+* topk_agrees() - a kernel's top-k selection against an fp64 top-k, order free only inside the error bound.
 """
 import math
 
@@ -18,10 +19,11 @@ U32 = 2.0 ** -24
 _U = {torch.float32: 2.0 ** -24, torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
 SAFETY = 2.0                     # one fixed factor over every modelled term; never tuned per test
 
-# sentinel payloads: quiet NaNs (fp) / a fixed word (int32) that differ from torch's canonical NaN (0x7FC00000 / 0x7E00 /
+# sentinel payloads: quiet NaNs (fp) / a fixed word (int32, int64) that differ from torch's canonical NaN (0x7FC00000 / 0x7E00 /
 # 0x7FC0), so neither a NaN prefill nor a computed NaN passes for "untouched"
 _SENT = {torch.float32: (torch.int32, 0x7FA5A5A5), torch.float16: (torch.int16, 0x7E5A),
-         torch.bfloat16: (torch.int16, 0x7FA5), torch.int32: (torch.int32, 0x5A5A5A5A)}
+         torch.bfloat16: (torch.int16, 0x7FA5), torch.int32: (torch.int32, 0x5A5A5A5A),
+         torch.int64: (torch.int64, 0x5A5A5A5A5A5A5A5A)}      # int64: no index or count (idx, load, counts64, splits) is that large
 GUARD_ROWS = 256
 ALIGN = 256                      # bytes: the view starts where a fresh torch allocation would
 
@@ -258,3 +260,296 @@ def attention_bwd_bounds(q, k, v, o, d_o, dq_ref, dk_ref, dv_ref, dtype):
 def sum_bound(terms_abs_sum, n, ref, out_dtype):
     """an fp32 sum of n terms (column sums, slab reductions, gather-sums, combine): n * u32 * sum|terms| + the store"""
     return SAFETY * (n * U32 * terms_abs_sum + store(out_dtype, ref))
+
+
+# ------------------------------------------------------------------------------------- the router (gate.hip, route.hip)
+# Every builder takes fp64 tensors of the values the kernel READ (the rounded x, w_gate, and - where a kernel consumes an
+# earlier kernel's output - that output as stored), so only the kernel's own arithmetic is charged.
+ETA_P = 2.0 ** -126              # absolute error of a probability near the fp32 underflow (a flushed or subnormal exp / quotient)
+
+
+def gate_logit_bound(x, w, bias=None):
+    """m3_gate_fwd's clean logits: acc = bias; acc = fma(x_d, w_de, acc) for d = 0 .. D-1 in order.  D fused roundings, each
+    of at most u32 times a partial sum bounded by |b| + sum_d |x_d w_de|, and the stored bias itself (one more term):
+      |logit - ref| <= (D + 1) u32 (|b| + |x| @ |w|)
+    x [T, D], w [D, E], bias [E] or None (fp64)."""
+    D = x.shape[-1]
+    a = x.abs() @ w.abs()
+    if bias is not None:
+        a = a + bias.abs()
+    return SAFETY * (D + 1) * U32 * a
+
+
+def noisy_logit_bound(clean_bound, noise=None, std=0.0, noisy=None):
+    """noisy = fl(clean + fl(noise * std)) (one mul, one add): the clean error plus u32 |noise std| + u32 |noisy| (the
+    SAFETY factor of clean_bound stays on it)"""
+    if noise is None or std == 0.0:
+        return clean_bound
+    return clean_bound + SAFETY * U32 * ((noise * std).abs() + noisy.abs())
+
+
+def softmax_bound(nz, delta):
+    """p_e = q_e / s, q_e = expf(nz_e - m), m = max nz, s = q_0 + ... + q_{E-1} in order, in fp32; nz [T, E] the fp64
+    logits the reference uses, delta [T, E] the bound on the kernel's logit error (0 where the kernel reads stored logits).
+      logit error: p_e = softmax(nz + d)_e = p_e (1 + d_e - sum_j p_j d_j + O(d^2)), so at most p_e 2 max_j delta_j;
+      nz_e - m rounded: u32 |nz_e - m| relative on q_e, and through s at most u32 max_j p_j |nz_j - m|;
+      expf a few ulps (4 u32), the sum of E positive terms E u32, the quotient (or reciprocal and product) 2 u32;
+      plus ETA_P where q or p underflow.
+      |p_e - ref_e| <= p_e (2 max delta + u32 (|nz_e - m| + max_j p_j |nz_j - m|) + (E + 6) u32) + ETA_P"""
+    E = nz.shape[-1]
+    m = nz.amax(-1, keepdim=True)
+    p = torch.softmax(nz, -1)
+    dm = delta.amax(-1, keepdim=True) if torch.is_tensor(delta) else delta
+    spread = (p * (nz - m).abs()).amax(-1, keepdim=True)
+    rel = 2 * dm + U32 * ((nz - m).abs() + spread) + (E + 6) * U32
+    return SAFETY * (p * rel + ETA_P)
+
+
+def load_prob_terms(clean, noisy, thr_in, thr_out, std):
+    """the Normal-CDF load term of one token and expert, evaluated in fp64 on the KERNEL's own clean / noisy logits and its
+    probability thresholds (thr_in = top_logits[:, k], thr_out = top_logits[:, k-1], [T, 1]):
+      is_in = noisy > thr_in ;  z = (clean - (thr_in if is_in else thr_out)) / std ;  term = Phi(z)
+    Returns (is_in, z, Phi(z), its error bound).  The kernel's z = fl(fl(clean - thr) * fl(1 / std)): three roundings,
+    |dz| <= 3 u32 |z|, carried by phi(z) |dz|; 0.5 erfc(-z / sqrt 2) adds a few ulps of the result (the scaling
+    product and erfcf itself: 6 u32 Phi):
+      |term - ref| <= phi(z) 3 u32 |z| + 6 u32 Phi(z) + ETA_P"""
+    is_in = noisy > thr_in
+    z = (clean - torch.where(is_in, thr_in, thr_out)) / std
+    Phi = 0.5 * torch.erfc(-z / math.sqrt(2.0))
+    phi = torch.exp(-0.5 * z * z) / math.sqrt(2 * math.pi)
+    return is_in, z, Phi, phi * 3 * U32 * z.abs() + 6 * U32 * Phi + ETA_P
+
+
+def cv2_reference(v):
+    """cv^2(v) = var(v, unbiased) / (mean(v)^2 + 1e-10) and its gradient, fp64 autograd; 0 and zeros for one expert"""
+    v = v.detach().double().clone().requires_grad_(True)
+    if v.numel() < 2:
+        return torch.zeros((), dtype=torch.float64), torch.zeros_like(v.detach())
+    cv = v.var(unbiased=True) / (v.mean() ** 2 + 1e-10)
+    (g,) = torch.autograd.grad(cv, v)
+    return cv.detach(), g
+
+
+def cv2_bound(v):
+    """the balance kernel's cv^2 of v [E] (fp64 copy of the kernel's OWN reduced importance / load, so only the loss
+    arithmetic is charged), evaluated in fp32 as written in gate.hip:
+      mean = (v_0 + ... + v_{E-1}) / E          dm <= (E + 1) u32 mean|v|
+      var  = sum_e (v_e - mean)^2 / (E - 1)     each (v_e - mean) is off by dm + u32 |v_e - mean|; the terms linear in dm
+                                                cancel (sum_e (v_e - mean) = 0), so
+                                                dvar <= ((E + 4) u32 S + E dm^2) / (E - 1),  S = sum_e (v_e - mean)^2
+      den  = mean^2 + 1e-10                     dden <= 2 |mean| dm + 3 u32 den
+      cv   = var / den                          dcv <= dvar / den + cv dden / den + u32 cv
+    As the variance goes to 0 the relative bound grows without limit: cv -> 0 while the E dm^2 / den floor
+    (about E^3 u32^2) stays - the absolute bound is what is checked.
+      grad_e = 2 (v_e - mean) / ((E - 1) den) - var 2 mean / (E den^2):
+        first term  : 2 (dm + 4 u32 |v_e - mean|) / ((E - 1) den) + |first| dden / den
+        second term : 2 |mean| dvar / (E den^2) + |second| (dm / |mean| + 2 dden / den + 5 u32)
+    Returns (cv bound (0-dim), grad bound [E]); zeros for one expert (the kernel writes exact zeros)."""
+    v = v.double()
+    E = v.numel()
+    if E < 2:
+        return torch.zeros((), dtype=torch.float64), torch.zeros_like(v)
+    mean = v.mean()
+    dm = (E + 1) * U32 * v.abs().mean()
+    c = v - mean
+    S = (c * c).sum()
+    var = S / (E - 1)
+    dvar = ((E + 4) * U32 * S + E * dm * dm) / (E - 1)
+    den = mean * mean + 1e-10
+    dden = 2 * mean.abs() * dm + 3 * U32 * den
+    cv = var / den
+    b_cv = dvar / den + cv * dden / den + U32 * cv
+    first = 2 * c / ((E - 1) * den)
+    second = var * 2 * mean / (E * den * den)
+    b1 = 2 * (dm + 4 * U32 * c.abs()) / ((E - 1) * den) + first.abs() * dden / den
+    b2 = 2 * mean.abs() * dvar / (E * den * den) + second.abs() * (dm / mean.abs().clamp_min(1e-300) + 2 * dden / den + 5 * U32)
+    return SAFETY * b_cv, SAFETY * (b1 + b2 + U32 * (first - second).abs())
+
+
+def gate_bwd_logits_bound(nz, dp_abs, dp_err, g_err, ref):
+    """m3_gate_bwd_logits: d_logits_e = p_e (dp_e - dot) + g_e, dot = sum_j p_j dp_j, all in fp32, from the STORED noisy
+    logits nz [T, E] (fp64 copies: no logit error is charged, the softmax is the kernel's own arithmetic of softmax_bound:
+    eps_p = (E + 6) u32 + u32 (|nz_e - m| + max_j p_j |nz_j - m|) relative, ETA_P absolute).  [T, E] fp64:
+      dp_abs  sum of |contributions| to dp_e: d_score, d_top, balance_scale d_importance, and a threshold term d_thr routed
+              to that expert (so A_e = dp_abs_e + sum_j p_j dp_abs_j bounds |dp_e - dot|)
+      dp_err  the kernel's error on dp_e: 5 u32 dp_abs_e (the adds and the balance-scale products) plus, at the expert a
+              threshold term lands on, that term's error (its fp32 sum over E experts: E u32 sum|g| + sum g_err)
+      g_err   the error of the CDF term g_e = d_load_prob_e bscale pdf(z) / std: pdf(z) moves by |z| pdf |dz|,
+              |dz| <= 3 u32 |z| (load_prob_terms), plus 8 u32 |g_e| for expf and the four products
+      |d - ref| <= p_e A_e (eps_p + (E + 3) u32) + p_e (dp_err_e + sum_j p_j dp_err_j) + g_err_e + u32 |ref| + ETA_P A_e
+    ((E + 3) u32: the dot product of E terms, the subtraction, the product and the add of g)."""
+    E = nz.shape[-1]
+    m = nz.amax(-1, keepdim=True)
+    p = torch.softmax(nz, -1)
+    spread = (p * (nz - m).abs()).amax(-1, keepdim=True)
+    eps_p = (E + 6) * U32 + U32 * ((nz - m).abs() + spread)
+    A = dp_abs + (p * dp_abs).sum(-1, keepdim=True)
+    t = (p * A * (eps_p + (E + 3) * U32) + p * (dp_err + (p * dp_err).sum(-1, keepdim=True)) + g_err + U32 * ref.abs()
+         + ETA_P * A)
+    return SAFETY * t
+
+
+def topk_agrees(idx, logits, bound):
+    """idx [T, k] (a kernel's selection, in selection order) against the fp64 logits [T, E] whose kernel-side error is
+    at most bound [T, E].  At every step j the chosen expert must not be beaten, beyond both bounds, by any expert not
+    chosen before it: logits[c] + bound[c] >= logits[e] - bound[e].  Indices must be distinct and in range.  Returns the
+    number of steps at which some other remaining expert lies within the bounds of the chosen one (a near-tie: either
+    order is accepted there), so that the caller can assert these are rare."""
+    idx = idx.long().cpu()
+    L = logits.double().cpu()
+    B = torch.as_tensor(bound).double().cpu().expand_as(L)
+    T, E = L.shape
+    k = idx.shape[1]
+    assert bool(((idx >= 0) & (idx < E)).all()), "expert index out of range"
+    taken = torch.zeros(T, E, dtype=torch.bool)
+    rows = torch.arange(T)
+    near = 0
+    for j in range(k):
+        c = idx[:, j]
+        assert not bool(taken[rows, c].any()), f"an expert is selected twice (step {j})"
+        lo = L[rows, c] - B[rows, c]
+        hi = L[rows, c] + B[rows, c]
+        others = ~taken
+        others[rows, c] = False
+        beat = others & (L - B > hi.unsqueeze(1))
+        if bool(beat.any()):
+            t = int(beat.any(1).nonzero()[0])
+            raise AssertionError(f"top-k step {j}, token {t}: expert {int(c[t])} chosen over "
+                                 f"{int(beat[t].nonzero()[0])} whose logit is larger beyond the bound")
+        near += int((others & (L + B >= lo.unsqueeze(1))).any(1).sum())
+        taken[rows, c] = True
+    return near
+
+
+def _blocks(v, nblk, rows=64):
+    """[T, E] -> per-64-row block sums [nblk, E] (fp64 / int64)"""
+    T, E = v.shape
+    pad = torch.zeros(nblk * rows - T, E, dtype=v.dtype, device=v.device)
+    return torch.cat((v, pad)).view(nblk, rows, E).sum(1)
+
+
+def check_gate_fwd(o, x, w, k, bias=None, noise=None, std=0.0):
+    """the value checks of one m3_gate_fwd call (the guards are the caller's).  o: dict of the kernel's outputs as torch
+    tensors (idx [T, k] int64, score [T, k], top_logits [T, min(k+1, E)], idx_next [T] or None, idx32 or None, clean /
+    noisy / gates [T, E] or None, part_importance / part_load / part_count / part_load_prob [nblk, E] or None);
+    x [T, D], w [D, E], bias [E], noise [T, E]: the rounded inputs the kernel read (any dtype; compared in fp64).
+    Returns (worst err / bound, near-ties of the top-k)."""
+    f64 = torch.float64
+    dev = o["idx"].device
+    x64, w64 = x.to(dev, f64), w.to(dev, f64)
+    b64 = None if bias is None else bias.to(dev, f64)
+    T, E = x64.shape[0], w64.shape[1]
+    kp = min(k + 1, E)
+    noisy_on = noise is not None and std != 0.0
+    clean64 = x64 @ w64 + (b64 if b64 is not None else 0.0)
+    cb = gate_logit_bound(x64, w64, b64)
+    nz64, nb = clean64, cb
+    if noisy_on:
+        nz64 = clean64 + noise.to(dev, f64) * float(torch.tensor(std, dtype=torch.float32))
+        nb = noisy_logit_bound(cb, noise.to(dev, f64), float(torch.tensor(std, dtype=torch.float32)), nz64)
+    worst = 0.0
+    idx = o["idx"]
+    near = topk_agrees(idx, nz64, nb) if T else 0
+    if o.get("idx32") is not None:
+        assert torch.equal(o["idx32"].long(), idx), "idx32 and idx disagree"
+    if o.get("clean") is not None:
+        worst = max(worst, assert_within(o["clean"], clean64, cb, "clean logits"))
+    if o.get("noisy") is not None:
+        want = o["clean"] + (noise * torch.tensor(std, dtype=torch.float32)) if noisy_on else o["clean"]
+        assert same_bits(o["noisy"], want), "noisy != fl32(clean + fl32(noise * std))"
+    pb = softmax_bound(nz64, nb)
+    p64 = torch.softmax(nz64, -1)
+    worst = max(worst, assert_within(o["score"], p64.gather(1, idx), pb.gather(1, idx), "score"))
+    sel = idx
+    if kp > k and o.get("idx_next") is None:
+        o = dict(o, top_logits=o["top_logits"][:, :k])       # (without idx_next only the first k columns are pinned)
+    elif kp > k:
+        nxt = o["idx_next"].long().unsqueeze(1)
+        assert not bool((nxt == idx).any(1).any()), "idx_next repeats a selected expert"
+        topk_agrees(torch.cat((idx, nxt), 1), nz64, nb)
+        sel = torch.cat((idx, nxt), 1)
+    worst = max(worst, assert_within(o["top_logits"], p64.gather(1, sel), pb.gather(1, sel), "top_logits"))
+    assert same_bits(o["top_logits"][:, :k].contiguous(), o["score"]), "top_logits[:, :k] != score"
+    dense_g = torch.zeros(T, E, dtype=torch.float32, device=dev).scatter(1, idx, o["score"])
+    if o.get("gates") is not None:
+        assert same_bits(o["gates"], dense_g), "gates != score scattered at idx (zeros elsewhere)"
+        worst = max(worst, assert_within(o["gates"], p64 * (dense_g != 0), pb, "gates"))
+    nblk = o["part_importance"].shape[0]
+    g64 = dense_g.double()
+    worst = max(worst, assert_within(o["part_importance"], _blocks(g64, nblk),
+                                     sum_bound(_blocks(g64.abs(), nblk), 64, _blocks(g64, nblk), torch.float32),
+                                     "part_importance"))
+    assert torch.equal(o["part_load"].long(), _blocks((dense_g > 0).long(), nblk)), "part_load != block count of gates > 0"
+    if o.get("part_count") is not None:
+        selm = torch.zeros(T, E, dtype=torch.long, device=dev).scatter(1, idx, 1)
+        assert torch.equal(o["part_count"].long(), _blocks(selm, nblk)), "part_count != block count of selected entries"
+    if o.get("part_load_prob") is not None:
+        top64 = o["top_logits"].double()
+        _, _, Phi, perr = load_prob_terms(o["clean"].double(), o["noisy"].double(), top64[:, k:k + 1], top64[:, k - 1:k],
+                                          float(torch.tensor(std, dtype=torch.float32)))
+        ref = _blocks(Phi, nblk)
+        worst = max(worst, assert_within(o["part_load_prob"], ref,
+                                         SAFETY * _blocks(perr, nblk) + sum_bound(ref, 64, ref, torch.float32),
+                                         "part_load_prob"))
+    return worst, near
+
+
+def gate_bwd_reference(noisy, idx, k, *, clean=None, top_logits=None, idx_next=None, d_score=None, d_top=None,
+                       d_importance=None, d_load_prob=None, balance_scale=1.0, noise_std=0.0):
+    """(d_logits fp64, its bound) of m3_gate_bwd_logits: fp64 autograd through the softmax of the kernel's STORED noisy
+    logits with the kernel's own idx / idx_next and its Normal-CDF decisions and thresholds.  The loss differentiated:
+      sum d_score p[idx] + sum d_top p[idx, idx_next] + bs sum_e d_imp_e sum_t gates_te
+      + bs sum_e d_lp_e sum_t Phi((clean_te - thr_t) / std),  thr = p[idx_next] (is_in) or p[idx[:, k-1]]
+    with clean the leaf and noisy = clean + (stored noisy - stored clean) (the gate's gradient reaches x through both).
+    balance_scale: the fp32 value the kernel multiplies by (bscale)."""
+    f64 = torch.float64
+    nzs = noisy.double()
+    T, E = nzs.shape
+    lp = d_load_prob is not None
+    base = clean.double() if lp else nzs
+    leaf = base.clone().requires_grad_(True)
+    nz = leaf + (nzs - base)
+    p = torch.softmax(nz, -1)
+    ix = idx.long()
+    loss = torch.zeros((), dtype=f64, device=nzs.device)
+    dp_abs = torch.zeros(T, E, dtype=f64, device=nzs.device)
+    dp_err = torch.zeros_like(dp_abs)
+    nxt = idx_next.long().unsqueeze(1) if (idx_next is not None and k < E) else None
+    bs = float(balance_scale)
+    if d_score is not None:
+        loss = loss + (d_score.double() * p.gather(1, ix)).sum()
+        dp_abs.scatter_add_(1, ix, d_score.double().abs())
+    if d_top is not None:
+        sel = torch.cat((ix, nxt), 1) if nxt is not None else ix
+        loss = loss + (d_top.double() * p.gather(1, sel)).sum()
+        dp_abs.scatter_add_(1, sel, d_top.double().abs())
+    if d_importance is not None:
+        di = d_importance.double() * bs
+        loss = loss + (di.unsqueeze(0).expand(T, E).gather(1, ix) * p.gather(1, ix)).sum()
+        dp_abs.scatter_add_(1, ix, di.abs().unsqueeze(0).expand(T, E).gather(1, ix))
+    g_err = torch.zeros_like(dp_abs)
+    if lp:
+        top = top_logits.double()
+        is_in = nzs > top[:, k:k + 1]
+        # the thresholds take the kernel's stored values, their gradient flows through the softmax
+        pin, pout = p.gather(1, nxt), p.gather(1, ix[:, k - 1:k])
+        thr = torch.where(is_in, top[:, k:k + 1] + (pin - pin.detach()), top[:, k - 1:k] + (pout - pout.detach()))
+        std = float(noise_std)
+        z = (leaf - thr) / std
+        Phi = 0.5 * torch.erfc(-z / math.sqrt(2.0))
+        dl = d_load_prob.double() * bs
+        loss = loss + (dl.unsqueeze(0) * Phi).sum()
+        zk = (clean.double() - torch.where(is_in, top[:, k:k + 1], top[:, k - 1:k])) / std
+        pdf = torch.exp(-0.5 * zk * zk) / math.sqrt(2 * math.pi)
+        g = (dl.unsqueeze(0) * pdf / std).abs()
+        g_err = g * (8 * U32 + zk.abs() * 3 * U32 * zk.abs())
+        for mask, tgt in ((is_in, nxt), (~is_in, ix[:, k - 1:k])):
+            gs = (g * mask).sum(1, keepdim=True)
+            dp_abs.scatter_add_(1, tgt, gs)
+            dp_err.scatter_add_(1, tgt, E * U32 * gs + (g_err * mask).sum(1, keepdim=True))
+    dp_err = dp_err + 5 * U32 * dp_abs
+    if loss.requires_grad:
+        (ref,) = torch.autograd.grad(loss, leaf)
+    else:
+        ref = torch.zeros_like(nzs)
+    return ref, gate_bwd_logits_bound(nzs, dp_abs, dp_err, g_err, ref)

@@ -71,6 +71,27 @@ def _calls(ops):
                                          dx=_t(T_, D_)),
                             lambda a: ops.gate_bwd_params(a["x"], a["w_gate"], a["d_logits"], d_w_gate=a["d_w_gate"], dx=a["dx"]),
                             ("x", "w_gate", "d_logits", "d_w_gate", "dx")),
+        "gate_fwd": (lambda: dict(x=_t(T_, D_, dtype=F16), w_gate=_t(D_, 8), logit_bias=_t(8), noise=_t(T_, 8),
+                                  loss_acc=_t(1)),
+                     lambda a: ops.gate_fwd(a["x"], a["w_gate"], K_, logit_bias=a["logit_bias"], noise=a["noise"],
+                                            noise_std=0.1, loss_acc=a["loss_acc"]),
+                     ("x", "w_gate", "logit_bias", "noise")),
+        "gate_bwd_logits": (lambda: dict(noisy=_t(T_, 8), clean=_t(T_, 8), top_logits=_t(T_, K_ + 1).abs(),
+                                         idx=torch.arange(K_, device="cuda").repeat(T_, 1),
+                                         idx_next=torch.full((T_,), K_, dtype=torch.int32, device="cuda"),
+                                         d_score=_t(T_, K_), d_top=_t(T_, K_ + 1), d_importance=_t(8), d_load_prob=_t(8),
+                                         out=_t(T_, 8), out_act=_t(T_, 8, dtype=F16), balance_scale_dev=_t(1)),
+                            lambda a: ops.gate_bwd_logits(a["noisy"], a["idx"], a["d_score"], a["d_importance"], K_,
+                                                          d_top=a["d_top"], idx_next=a["idx_next"],
+                                                          d_load_prob=a["d_load_prob"], clean=a["clean"],
+                                                          top_logits=a["top_logits"], noise_std=0.5, out=a["out"],
+                                                          balance_scale_dev=a["balance_scale_dev"], out_act=a["out_act"]),
+                            ("noisy", "clean", "top_logits", "idx", "idx_next", "d_score", "d_top", "d_importance",
+                             "d_load_prob", "out", "out_act")),
+        "ep_plan": (lambda: dict(send=torch.full((3 * 4,), 5, dtype=torch.int64, device="cuda"),
+                                 recv=torch.full((3 * 4,), 7, dtype=torch.int64, device="cuda"),
+                                 buf=torch.zeros(3 * 4 * 7, dtype=torch.int32, device="cuda")),
+                    lambda a: ops.ep_plan(a["send"], a["recv"], 3, 4, a["buf"]), ("send", "recv", "buf")),
         "layernorm_bwd_reduce": (lambda: dict(ws=_t(3, 2, ops.lib().m3_ln_bwd_blocks(T_, D_), D_)),
                                  lambda a: ops.layernorm_bwd_reduce(a["ws"], ops.lib().m3_ln_bwd_blocks(T_, D_), D_,
                                                                     ops.LnGradTable([(_t(D_), _t(D_)) for _ in range(3)], "cuda"),
@@ -121,3 +142,17 @@ def test_wrappers_reject_bad_tensors_before_launch(ops, name):
     args[targets[0]] = args[targets[0]].cpu()
     with pytest.raises(ops._lib.M3Error):
         call(args)
+
+
+def test_one_element_operands_are_sized(ops):
+    """loss_acc and balance_scale_dev must hold exactly one f32 (the column trick of _non_contiguous does not apply)"""
+    x, w = _t(T_, D_, dtype=F16), _t(D_, 8)
+    with pytest.raises(ops._lib.M3Error):
+        ops.gate_fwd(x, w, K_, loss_acc=_t(2))
+    with pytest.raises(ops._lib.M3Error):
+        ops.gate_fwd(x, w, K_, loss_acc=_t(1, dtype=torch.float16))
+    idx = torch.arange(K_, device="cuda").repeat(T_, 1)
+    with pytest.raises(ops._lib.M3Error):
+        ops.gate_bwd_logits(_t(T_, 8), idx, _t(T_, K_), _t(8), K_, balance_scale_dev=_t(2))
+    with pytest.raises(ops._lib.M3Error):
+        ops.gate_bwd_logits(_t(T_, 8), idx.int(), _t(T_, K_), _t(8), K_)          # int32 idx is not reinterpreted

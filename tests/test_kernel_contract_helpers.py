@@ -131,3 +131,211 @@ def test_sentinels_are_nans_torch_does_not_produce():
         assert bool(torch.isnan(s).all())
         assert not kc.same_bits(s, torch.full((1,), float("nan"), dtype=dt))
         assert kc.same_bits(s, s.clone())
+
+
+def test_int64_sentinel_is_a_word_no_index_or_count_takes():
+    s = kc.sentinel_like(torch.empty(3, dtype=torch.int64))
+    assert kc.same_bits(s, s.clone()) and int(s[0]) > 2 ** 62
+    C, check = kc.guarded(4, 3, torch.int64, ld=5, device=DEV)
+    C.fill_(0)
+    check()
+    torch.as_strided(C, (4, 5), (5, 1))[1, 4] = 7
+    with pytest.raises(AssertionError, match=r"row 1, col 4.*row padding"):
+        check()
+
+
+# ----------------------------------------------------------------------------------------------------- the gate stand-in
+# A plain torch restatement of m3_gate_fwd / m3_gate_bwd_logits (the pinned fma chain emulated in fp64: every product of
+# two fp32 values is exact there and each step rounds to fp32, as fmaf does - up to a double rounding no input here hits),
+# passing every check of kernel_contract.check_gate_fwd / gate_bwd_reference; each injected defect is one the GPU
+# contract tests of the router must catch.
+GT, GD, GE, GK = 300, 32, 12, 3
+
+
+def gate_standin(x, w, k, bias, noise, std, out, T_alloc=None, defect=None):
+    """writes out[...] (guarded views) like the kernel"""
+    T, D = x.shape
+    E = w.shape[1]
+    acc = (bias.double() if bias is not None else torch.zeros(E, dtype=torch.float64)).float().expand(T, E).clone()
+    for d in range(D):
+        acc = (x[:, d:d + 1].double() * w[d].double() + acc.double()).float()
+    clean = acc
+    noisy = clean + noise * torch.tensor(std, dtype=torch.float32) if (noise is not None and std != 0) else clean
+    m = noisy.max(1, keepdim=True).values
+    q = torch.exp(noisy - m)
+    s = (q[:, :-1] if defect == "pad_denominator" else q).sum(1, keepdim=True)
+    p = q / s
+    kp = min(k + 1, E)
+    order = torch.sort(noisy.flip(1) if defect == "ties_high" else noisy, dim=1, descending=True, stable=True).indices
+    if defect == "ties_high":
+        order = E - 1 - order
+    sel = order[:, :kp]
+    out["idx"].copy_(sel[:, :k])
+    out["idx32"].copy_(sel[:, :k].int())
+    out["score"].copy_(p.gather(1, sel[:, :k]))
+    out["top_logits"].copy_(p.gather(1, sel))
+    if kp > k:
+        out["idx_next"].copy_(sel[:, k].int())
+    gates = torch.zeros(T, E).scatter(1, sel[:, :k], p.gather(1, sel[:, :k]))
+    out["clean"].copy_(clean); out["noisy"].copy_(noisy); out["gates"].copy_(gates)
+    if defect == "dense_past_T":
+        g = out["gates"]
+        torch.as_strided(g, (T + 1, E), (E, 1))[T] = 0.0
+    nblk = out["part_load"].shape[0]
+    selm = torch.zeros(T, E, dtype=torch.long).scatter(1, sel[:, :k], 1)
+    out["part_importance"].copy_(kc._blocks(gates.double(), nblk).float())
+    out["part_load"].copy_(kc._blocks(selm if defect == "load_counts_selected" else (gates > 0).long(), nblk).int())
+    out["part_count"].copy_(kc._blocks(selm, nblk).int())
+    if out.get("part_load_prob") is not None:
+        thr_in, thr_out = p.gather(1, sel[:, k:k + 1]), p.gather(1, sel[:, k - 1:k])
+        z = (clean - torch.where(noisy > thr_in, thr_in, thr_out)) * (1.0 / torch.tensor(std, dtype=torch.float32))
+        out["part_load_prob"].copy_(kc._blocks((0.5 * torch.erfc(-z * 0.70710678)).double(), nblk).float())
+
+
+def gate_bwd_standin(noisy, clean, top, idx, idx_next, k, d_score, d_top, d_imp, d_lp, bs, std, out, out_act, defect=None):
+    T, E = noisy.shape
+    m = noisy.max(1, keepdim=True).values
+    q = torch.exp(noisy - m)
+    p = q * (1.0 / q.sum(1, keepdim=True))
+    g = torch.zeros(T, E)
+    dthr_in = torch.zeros(T); dthr_out = torch.zeros(T)
+    if d_lp is not None:
+        is_in = noisy > top[:, k:k + 1]
+        z = (clean - torch.where(is_in, top[:, k:k + 1], top[:, k - 1:k])) * (1.0 / torch.tensor(std, dtype=torch.float32))
+        g = d_lp * bs * (0.3989422804014327 * torch.exp(-0.5 * z * z)) * (1.0 / torch.tensor(std, dtype=torch.float32))
+        dthr_in = -(g * is_in).sum(1); dthr_out = -(g * ~is_in).sum(1)
+    dp = torch.zeros(T, E)
+    v = d_score.clone() + (d_top[:, :k] if d_top is not None else 0) + (d_imp[idx] * bs if d_imp is not None else 0)
+    v[:, k - 1] += dthr_out
+    dp.scatter_add_(1, idx, v)
+    if k < E:
+        vn = (d_top[:, k] if d_top is not None else 0) + (0 if defect == "drop_d_thr_in" else dthr_in)
+        dp.scatter_add_(1, idx_next.long().unsqueeze(1), torch.as_tensor(vn).expand(T).unsqueeze(1).float())
+    dl = p * (dp - (dp * p).sum(1, keepdim=True)) + g
+    out.copy_(dl)
+    if out_act is not None:
+        if defect == "act_truncated":
+            out_act.copy_((dl.view(torch.int32) & ~0xFFFF).view(torch.float32).bfloat16())
+        else:
+            out_act.copy_(dl.bfloat16())
+
+
+@pytest.fixture(scope="module")
+def gate_inputs():
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(GT, GD, generator=g)
+    w = torch.randn(GD, GE, generator=g) * 0.3
+    w[:, 7] = w[:, 2]                                  # exact ties: experts 2 and 7 always share a logit
+    bias = torch.randn(GE, generator=g) * 0.2
+    bias[7] = bias[2]
+    bias[0:2] = -200.0                                 # two experts whose probabilities underflow to 0: with k = E - 1 one
+                                                       # of them is selected all the same
+    noise = torch.randn(GT, GE, generator=g)
+    return x, w, bias, noise
+
+
+def run_gate(gate_inputs, defect=None, k=GK, noisy=True):
+    """(all checks pass, rel-L2 of the dense gates < 1e-4)"""
+    x, w, bias, noise = gate_inputs
+    std = 0.05 if noisy else 0.0
+    nblk = -(-GT // 64)
+    kp = min(k + 1, GE)
+    out, checks = {}, []
+    for name, (r, c, dt) in {"idx": (GT, k, torch.int64), "idx32": (GT, k, torch.int32), "score": (GT, k, torch.float32),
+                             "top_logits": (GT, kp, torch.float32), "idx_next": (GT, 1, torch.int32),
+                             "clean": (GT, GE, torch.float32), "noisy": (GT, GE, torch.float32),
+                             "gates": (GT, GE, torch.float32), "part_importance": (nblk, GE, torch.float32),
+                             "part_load": (nblk, GE, torch.int32), "part_count": (nblk, GE, torch.int32),
+                             "part_load_prob": (nblk, GE, torch.float32)}.items():
+        v, chk = kc.guarded(r, c, dt, device=DEV)
+        out[name] = v.view(GT) if name == "idx_next" else v
+        checks.append((name, chk))
+    if not noisy:
+        out["part_load_prob"] = None
+    snap = kc.snapshot(x=x, w=w, bias=bias, noise=noise)
+    gate_standin(x, w, k, bias, noise if noisy else None, std, out, defect=defect)
+    kc.unchanged(snap)
+    from oracle import c_oracle
+    c = c_oracle.gate_fwd(x.numpy(), w.numpy(), k, bias=bias.numpy(), noise=noise.numpy() if noisy else None, std=std)
+    ref_g = torch.softmax(torch.tensor(c["noisy"]).double(), 1)
+    ref_g = torch.zeros_like(ref_g).scatter(1, torch.tensor(c["idx"]), ref_g.gather(1, torch.tensor(c["idx"])))
+    ok_rel = rel(out["gates"], ref_g) < 1e-4
+    try:
+        for name, chk in checks:
+            chk(what=name)
+        assert torch.equal(out["idx"], torch.tensor(c["idx"])), "idx differs from the C oracle"
+        assert kc.same_bits(out["clean"], torch.tensor(c["clean"])), "clean differs from the C oracle"
+        worst, near = kc.check_gate_fwd(out, x, w, k, bias=bias, noise=noise if noisy else None, std=std)
+    except AssertionError:
+        return False, ok_rel
+    return True, ok_rel
+
+
+def run_gate_bwd(gate_inputs, defect=None, k=GK):
+    x, w, bias, noise = gate_inputs
+    std = 0.05
+    out, chk = {}, None
+    o = {n: torch.empty(0) for n in ()}
+    T, E, kp = GT, GE, min(k + 1, GE)
+    fo = dict(idx=torch.empty(T, k, dtype=torch.int64), idx32=torch.empty(T, k, dtype=torch.int32),
+              score=torch.empty(T, k), top_logits=torch.empty(T, kp), idx_next=torch.empty(T, dtype=torch.int32),
+              clean=torch.empty(T, E), noisy=torch.empty(T, E), gates=torch.empty(T, E),
+              part_importance=torch.empty(5, E), part_load=torch.empty(5, E, dtype=torch.int32),
+              part_count=torch.empty(5, E, dtype=torch.int32), part_load_prob=torch.empty(5, E))
+    gate_standin(x, w, k, bias, noise, std, fo)
+    g = torch.Generator().manual_seed(9)
+    d_score, d_top = torch.randn(T, k, generator=g), torch.randn(T, kp, generator=g)
+    d_imp, d_lp = torch.randn(E, generator=g) * 1e-2, torch.randn(E, generator=g)
+    bs = 0.5
+    dl, check = kc.guarded(T, E, torch.float32, device=DEV)
+    act, acheck = kc.guarded(T, E, torch.bfloat16, device=DEV)
+    gate_bwd_standin(fo["noisy"], fo["clean"], fo["top_logits"], fo["idx"], fo["idx_next"], k, d_score, d_top, d_imp, d_lp,
+                     bs, std, dl, act, defect=defect)
+    ref, bound = kc.gate_bwd_reference(fo["noisy"], fo["idx"], k, clean=fo["clean"], top_logits=fo["top_logits"],
+                                       idx_next=fo["idx_next"], d_score=d_score, d_top=d_top, d_importance=d_imp,
+                                       d_load_prob=d_lp, balance_scale=bs, noise_std=std)
+    ok_rel = rel(dl, ref) < 1e-4
+    try:
+        check(); acheck()
+        worst = kc.assert_within(dl, ref, bound, "d_logits")
+        assert kc.same_bits(act, dl.to(torch.bfloat16)), "d_logits_act is not d_logits rounded to nearest even"
+    except AssertionError:
+        return False, ok_rel, None
+    return True, ok_rel, worst
+
+
+def test_the_clean_gate_standin_passes_every_check(gate_inputs):
+    assert run_gate(gate_inputs) == (True, True)
+    assert run_gate(gate_inputs, noisy=False) == (True, True)
+    assert run_gate(gate_inputs, k=GE - 1)[0]
+    ok, ok_rel, worst = run_gate_bwd(gate_inputs)
+    assert ok and ok_rel, (ok, ok_rel)
+    assert 1e-3 < worst < 1, f"the backward bound is not tight enough to mean anything: worst err/bound {worst}"
+
+
+def test_the_gate_fixture_has_the_edges_the_defects_need(gate_inputs):
+    x, w, bias, noise = gate_inputs
+    from oracle import c_oracle
+    c = c_oracle.gate_fwd(x.numpy(), w.numpy(), GE - 1, bias=bias.numpy())
+    assert (c["score"] == 0).all(1).sum() == 0 and (c["score"] == 0).any(), "a selected probability must underflow"
+    idx = torch.tensor(c["idx"])
+    assert bool(((idx == 2) | (idx == 7)).any())      # the tied pair is selected
+
+
+@pytest.mark.parametrize("defect,kw", [("ties_high", {"noisy": False}), ("pad_denominator", {}), ("dense_past_T", {}),
+                                       ("load_counts_selected", {"k": GE - 1})])
+def test_each_injected_gate_defect_is_caught(gate_inputs, defect, kw):
+    ok, _ = run_gate(gate_inputs, defect, **kw)
+    assert not ok, f"defect {defect} went unnoticed"
+
+
+@pytest.mark.parametrize("defect", ["drop_d_thr_in", "act_truncated"])
+def test_each_injected_gate_backward_defect_is_caught(gate_inputs, defect):
+    ok, _, _ = run_gate_bwd(gate_inputs, defect)
+    assert not ok, f"defect {defect} went unnoticed"
+
+
+def test_relative_l2_alone_misses_gate_defects_the_contract_catches(gate_inputs):
+    missed = [d for d in ("dense_past_T", "load_counts_selected") if run_gate(gate_inputs, d, k=GE - 1)[1]]
+    missed += [d for d in ("act_truncated",) if run_gate_bwd(gate_inputs, d)[1]]
+    assert "dense_past_T" in missed and "act_truncated" in missed, missed
