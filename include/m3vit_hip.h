@@ -366,6 +366,42 @@ int m3_combine_gate_bwd(const void *dxe, int dtype, int64_t T, int k, int D, con
 int m3_gather_rows(const void *src, int dtype, const int32_t *idx, int div, int64_t nout, int k,
                    int D, void *dst, void *stream);
 
+/* ------------------------------------------------------- routing statistics
+ * What a MoE Block reports in `last_moe_analysis` after every forward
+ * (models/moe/ckpt/vision_transformer_moe.py:461-478 inside the checkpointed body, :546-562 for expert_load_cv), which
+ * VisionTransformerMoE.forward folds into `latest_moe_stats` (:795-880) - computed on the device, inside the pass, into
+ * one record the host copies only when somebody asks (the reference reads seven scalars per MoE block with .item()).
+ * Inputs, all read-only: score f32 [T,k] and gates f32 [T,E] (the gate's top-k probabilities, dense: p at the selected
+ * experts, 0 elsewhere), clean f32 [T,E] (clean_logits), h [T,D] (norm2(x), row stride ldh elements) and y [T*k,D] (the
+ * token-major expert outputs, row stride ldy) in the activation dtype, and the load vector [E] of the block's balance
+ * loss as EITHER load_f32 (the Normal-CDF form of noisy training) OR load_i64 (the counts), the other NULL.
+ * m = sum_j score[t,j] * y[t*k+j] is the layer output before mlp_drop / DropPath / the residual (fp32 fma, j ascending).
+ * The record is M3_MOE_STATS_HIST + E four-byte words:
+ *   f32 [M3_MOE_STATS_ENTROPY_SUM]  sum_t sum_e -p ln(max(p, 1e-12))
+ *   f32 [M3_MOE_STATS_TOP1_SUM]     sum_t max_e p[t,e]
+ *   f32 [M3_MOE_STATS_CLEAN_STD]    mean_t of the population std over E of clean[t,:]   (0 for T = 0)
+ *   f32 [M3_MOE_STATS_NORM_RATIO]   |m|_2 / (|h|_2 + 1e-12), Frobenius norms over [T,D]
+ *   f32 [M3_MOE_STATS_LOAD_CV]      var_pop(load) / (mean(load)^2 + 1e-10); 0 for E <= 1
+ *   f32 [M3_MOE_STATS_M_SUMSQ], [M3_MOE_STATS_H_SUMSQ]   the two sums of squares behind the ratio
+ *   i32 [M3_MOE_STATS_TOKENS]       T
+ *   i32 [M3_MOE_STATS_HIST + e]     #{t : p[t,e] > 0}  (a selected probability that underflowed to 0 does not count)
+ * ws f32 [m3_moe_stats_ws_elems(T,E)]: per-workgroup partials, added in a fixed order by a second one-workgroup launch -
+ * no atomics, two runs on the same inputs give the same bits.  E in [1,64], 1 <= k <= E, T < 2^31; rows of h and y are
+ * 16-byte multiples at 16-byte aligned addresses. */
+#define M3_MOE_STATS_ENTROPY_SUM 0
+#define M3_MOE_STATS_TOP1_SUM 1
+#define M3_MOE_STATS_CLEAN_STD 2
+#define M3_MOE_STATS_NORM_RATIO 3
+#define M3_MOE_STATS_LOAD_CV 4
+#define M3_MOE_STATS_M_SUMSQ 5
+#define M3_MOE_STATS_H_SUMSQ 6
+#define M3_MOE_STATS_TOKENS 7
+#define M3_MOE_STATS_HIST 8
+int64_t m3_moe_stats_ws_elems(int64_t T, int E);
+int m3_moe_stats(const float *score, const float *clean, const float *gates, const void *h, int64_t ldh,
+                 const void *y, int64_t ldy, int dtype, const float *load_f32, const int64_t *load_i64,
+                 int64_t T, int E, int k, int D, float *ws, void *record, void *stream);
+
 /* ----------------------------------------------------------- LayerNorm (a9)
  * nn.LayerNorm(D, eps) on the fp32 residual stream, output in the act dtype
  * (vision_transformer_moe.py:441-442, eps 1e-6 :567).  Saves mean/rstd fp32 [T]. */

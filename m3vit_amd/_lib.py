@@ -139,6 +139,8 @@ SIGNATURES = {
     "m3_combine_fwd": (c_int, [_V, _I, _V, _V, _L, _I, _I, _V, _V]),
     "m3_combine_bwd": (c_int, [_V, _V, _I, _V, _L, _I, _I, _V, _V, _V]),
     "m3_combine_gate_bwd": (c_int, [_V, _I, _L, _I, _I, _V, _V, _I, _V, _I, _V]),
+    "m3_moe_stats_ws_elems": (c_int64, [_L, _I]),
+    "m3_moe_stats": (c_int, [_V, _V, _V, _V, _L, _V, _L, _I, _V, _V, _L, _I, _I, _I, _V, _V, _V]),
     "m3_gather_rows": (c_int, [_V, _I, _V, _I, _L, _I, _I, _V, _V]),
     "m3_layernorm_fwd": (c_int, [_V, _L, _I, _V, _V, _F, _V, _I, _V, _V, _V]),
     "m3_ln_bwd_blocks": (c_int, [_L, _I]),

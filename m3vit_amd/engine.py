@@ -27,6 +27,7 @@ import torch
 
 import os
 
+from . import moe_stats as _ms
 from . import ops
 from .ops import M3_ACT_GELU
 
@@ -44,7 +45,7 @@ class BackboneEngine:
     def __init__(self, cfg, params: Dict[str, torch.Tensor], batch: int, dtype=torch.float16,
                  device="cuda:0", ep_group=None, ep_world: int = 1, ep_rank: int = 0, share: "BackboneEngine" = None,
                  wgrad_stream: bool = False, checkpoint: bool = False, ep_capacity: float = 0.0,
-                 experts_are_local: bool = False, ep_chunks: int = 1, ep_native: bool = False):
+                 experts_are_local: bool = False, ep_chunks: int = 1, ep_native: bool = False, moe_stats: bool = False):
         """params: GLOBAL parameters (all E experts).  With ep_world > 1 this rank keeps experts
         [ep_rank*E/W, (ep_rank+1)*E/W) (utils/common_config.py:179-185) and exchanges routed rows with
         the other ranks over torch.distributed (RCCL) - see _experts_fwd_ep.
@@ -75,7 +76,13 @@ class BackboneEngine:
         m3_ep_return) instead of torch.distributed's all_to_all_single.
         experts_are_local (with ep_world > 1): the expert tensors in `params` are already this rank's slice [E / W, ..] (a
         module built the way utils/common_config.py:179-185 builds it: moe_experts // world_size experts per rank) and are
-        taken as they are - in place - instead of being cut out of global tensors."""
+        taken as they are - in place - instead of being cut out of global tensors.
+        moe_stats (off by default: no buffer, no launch): every forward also leaves each MoE block's routing statistics -
+        the reference's `last_moe_analysis` (vision_transformer_moe.py:461-478,546-562) - in a device-resident record
+        (m3_moe_stats, launched behind the block's combine on the pass's stream, also inside a captured pass); nothing is
+        read by the host until moe_stats() is called.  Under expert parallelism a rank reports its own tokens (every exchange
+        variant brings the expert outputs home token-major, which is what the kernel reads)."""
+        self.moe_stats_on = bool(moe_stats)
         assert not (checkpoint and wgrad_stream), "checkpoint mode re-uses the activation buffers a wgrad stream may still read"
         self.checkpoint = bool(checkpoint)
         assert dtype in (torch.float16, torch.bfloat16, torch.float32), "activation dtype: float16, bfloat16 or float32"
@@ -271,6 +278,12 @@ class BackboneEngine:
         self.s_dl_t = self._e(T, self.E)
         self.s_dl = self._e(T, self.E, dtype=f32)
         self.cv_acc = torch.zeros(1, dtype=f32, device=self.dev)
+        # routing statistics (opt-in): one record per MoE block + the partials workspace of m3_moe_stats
+        self.stats_rec = self.ws_stats = None
+        self.stats_row = {i: j for j, i in enumerate(i for i in range(self.depth) if self.is_moe[i])}
+        if self.moe_stats_on and self.stats_row:
+            self.stats_rec = torch.zeros(len(self.stats_row), _ms.record_words(self.E), dtype=torch.int32, device=self.dev)
+            self.ws_stats = self._e(ops.moe_stats_ws_elems(T, self.E), dtype=f32)
         if self.ep_world > 1:
             # expert-parallel exchange plans: one regroup index per MoE block (kept for the backward; a rank can
             # receive at most what all ranks route) and the pinned landing buffer of the split sizes
@@ -475,7 +488,23 @@ class BackboneEngine:
                 a["sm_tok"] = sm.view(B, 1).expand(B, N).reshape(T, 1).contiguous()
                 a["score_s"] = g["score"] * a["sm_tok"]
             ops.combine_fwd(a["y"], a["score_s"] if sm is not None else g["score"], a["x1"], a["x2"])
+            if self.stats_rec is not None and loss_acc is not None:      # (not in the checkpoint recompute: counted once)
+                # the UNSCALED score: m is the layer output before DropPath, a dropped sample still reports its experts
+                ops.moe_stats(g["score"], g["clean"], g["gates"], a["h2"], a["y"],
+                              g["load_prob"] if g["load_prob"] is not None else g["load"],
+                              self.stats_rec[self.stats_row[i]], ws=self.ws_stats)
         return a["x2"]
+
+    def moe_stats(self):
+        """The routing statistics of the last forward: ({block index: the block's dict}, the backbone dict), in the
+        reference's key names and Python types (m3vit_amd.moe_stats).  ONE device-to-host copy of the records, made here
+        and only here; None when the engine was built without moe_stats or has no MoE block."""
+        if self.stats_rec is None:
+            return None
+        static = _ms.static_fields(self.D, self.cfg.mlp_ratio, self.cfg.moe_mlp_ratio, self.k)
+        rows = _ms.read_records(self.stats_rec, self.E, static)
+        blocks = {i: rows[j] for i, j in self.stats_row.items()}
+        return blocks, _ms.aggregate([blocks[i] for i in sorted(blocks)], self.B * max(self.N - 1, 0))
 
     def forward(self, images: torch.Tensor, task_id: Optional[int], tsf_bias=None, noises=None, path_scales=None,
                 stem_of: "BackboneEngine" = None):

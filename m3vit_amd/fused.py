@@ -119,6 +119,7 @@ class FusedBackbone:
         # autograd delivery (see _deliver): the nodes still waiting for their backward, the backward call (autograd graph
         # task) that is summing its passes, and the fresh buffer it sums into
         self.ag_nodes, self.ag_task, self.ag_acc = [], None, None
+        self.moe_stats, self.stats_slot = False, None
 
     # a copy of the model (copy.deepcopy for an EMA twin, torch.save of the whole module) gets no executor state - contexts,
     # streams and graphs are rebuilt at its first call
@@ -194,6 +195,8 @@ class FusedBackbone:
         # experts sharded over the ranks (world_size > 1, utils/common_config.py:179-185): the module holds this rank's
         # moe_experts // world_size experts, the executor exchanges the routed rows (engine._experts_fwd_ep).  The exchange
         # reads its split sizes on the host, so these passes run eagerly (no hipGraph)
+        self.moe_stats = bool(getattr(model, "moe_stats", False))
+        self.stats_slot = None                   # the context of the most recent forward CALL (its records are that call's)
         self.ep = {}
         if model.world_size > 1:
             import torch.distributed as dist
@@ -202,7 +205,7 @@ class FusedBackbone:
             assert dist.get_world_size(group) == model.world_size, "the layer's world_size must be the expert group's size"
             self.graph = False
         eng0 = BackboneEngine(cfg, params, batch=B, dtype=model.act_dtype, device=str(device),
-                              checkpoint=bool(model.use_checkpointing), **self.ep)
+                              checkpoint=bool(model.use_checkpointing), moe_stats=self.moe_stats, **self.ep)
         for n, p in named.items():
             if eng0.params[n].data_ptr() != p.data_ptr():
                 raise RuntimeError(f"fused backbone: parameter {n} must be a contiguous fp32 CUDA tensor")
@@ -244,7 +247,7 @@ class FusedBackbone:
         if slots is None:
             e0 = self.base_eng
             eng = e0 if e0.B == B else BackboneEngine(self.cfg, None, batch=B, dtype=e0.dt, device=str(self.device), share=e0,
-                                                      checkpoint=e0.checkpoint, **self.ep)
+                                                      checkpoint=e0.checkpoint, moe_stats=self.moe_stats, **self.ep)
             slots = [_Slot(0, eng, self.device)]
         while len(self.slot_sets) > 2:
             self.slot_sets.pop(next(iter(self.slot_sets)))
@@ -260,7 +263,7 @@ class FusedBackbone:
                                "call backward() (or drop the outputs) before running more")
         e0 = self.base_eng
         eng = BackboneEngine(self.cfg, None, batch=self.batch, dtype=e0.dt, device=str(self.device), share=e0,
-                             checkpoint=e0.checkpoint, **self.ep)
+                             checkpoint=e0.checkpoint, moe_stats=self.moe_stats, **self.ep)
         s = _Slot(len(self.slots), eng, self.device)
         self.slots.append(s)
         return s
@@ -344,7 +347,20 @@ class FusedBackbone:
         main.wait_stream(slot.stream)
         tok.record_stream(main)
         cv.record_stream(main)
+        self.stats_slot = slot
         return tok, cv
+
+    def read_moe_stats(self):
+        """The routing statistics of the most recent forward call of the module - (block dicts, backbone dict) as
+        BackboneEngine.moe_stats() returns them, or None.  The records live in the context ("slot") that ran that call: a
+        pass started ahead of its call writes another context's records, and the context of a call is handed to no other
+        pass before the next call (passes are only ever started inside a forward call, on other contexts than the call's
+        own), so what is read is that call's, whatever ran in between.  The one device-to-host copy happens here."""
+        slot = self.stats_slot
+        if slot is None or not self.moe_stats:
+            return None
+        torch.cuda.current_stream().wait_stream(slot.stream)
+        return slot.eng.moe_stats()
 
     # ------------------------------------------------------------------ forward without autograd (evaluation)
     def _nograd_pass(self, slot, task_id, images, model):
@@ -421,6 +437,7 @@ class FusedBackbone:
         tok.record_stream(main)
         cv.record_stream(main)
         slot.busy = False
+        self.stats_slot = slot
         return tok, cv
 
     def _launch(self, task_id, images, main, grads):

@@ -692,6 +692,38 @@ def combine_gate_bwd(dxe, k, d_logits, w_gate, dh):
     return dh
 
 
+def moe_stats_ws_elems(T, E) -> int:
+    return int(lib().m3_moe_stats_ws_elems(T, E))
+
+
+def moe_stats(score, clean, gates, h, y, load, record, ws=None):
+    """One MoE block's routing statistics (m3_moe_stats) into `record`, an int32 tensor of moe_stats.record_words(E) words
+    (layout: include/m3vit_hip.h; m3vit_amd.moe_stats.parse_record reads it).  score [T,k], clean / gates [T,E] f32;
+    h [T,D] and y [T*k,D] in one activation dtype, rows may be strided; load [E] float32 or int64.  Nothing is read back."""
+    T, k = _dims(score, 2, "score")
+    E = _dims(gates, 2, "gates")[1]
+    D = h.shape[-1]
+    _req(score, torch.float32, "score"); _req(gates, torch.float32, "gates", T * E); _req(clean, torch.float32, "clean", T * E)
+    for t_, name, rows in ((h, "h", T), (y, "y", T * k)):
+        if not t_.is_cuda or t_.dtype not in _DT or t_.dtype != h.dtype or t_.dim() != 2 or tuple(t_.shape) != (rows, D) or \
+                (rows > 1 and t_.stride(0) < D) or (D > 1 and t_.stride(1) != 1):
+            raise _lib.M3Error(f"{name} must be [{rows}, {D}] {h.dtype} with unit column stride, got {tuple(t_.shape)} "
+                               f"{t_.dtype} strides {tuple(t_.stride())}")
+    if load.dtype not in (torch.float32, torch.int64):
+        raise _lib.M3Error(f"load must be float32 or int64, got {load.dtype}")
+    _req(load, load.dtype, "load", E)
+    _req(record, torch.int32, "record", min_numel=8 + E)
+    need = moe_stats_ws_elems(T, E)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.float32, device=score.device)
+    _req(ws, torch.float32, "ws", min_numel=need)
+    lf, li = (load, None) if load.dtype == torch.float32 else (None, load)
+    check(lib().m3_moe_stats(_p(score), _p(clean), _p(gates), _p(h), h.stride(0) if T > 1 else D, _p(y),
+                             y.stride(0) if T * k > 1 else D, dt_code(h.dtype), _p(lf), _p(li), T, E, k, D, _p(ws),
+                             _p(record), _stream()), "m3_moe_stats")
+    return record
+
+
 def gather_rows(src, idx, dst, div=1, k=1):
     """dst[i] = sum_{j<k} src[idx[i*k+j] // div]."""
     nout, D = _dims(dst, 2, "dst")

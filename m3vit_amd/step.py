@@ -39,8 +39,10 @@ class MultiTaskStep:
     def __init__(self, cfg, params, batch: int, dtype=torch.float16, device="cuda:0", tasks=None, cv_weight: float = 0.01,
                  parallel_tasks: bool = True, graph: bool = True, world: int = 1, rank: int = 0, expert_parallel: bool = False,
                  wgrad_streams: bool = False, dp_parts: int = 6, checkpoint: bool = False, share_stem: bool = False,
-                 ep_capacity: float = 0.0, ep_chunks: int = 1, ep_native: bool = False):
-        """ep_capacity (expert parallel only; 0 = the exact exchange): fixed row capacity of the exchange as a multiple of
+                 ep_capacity: float = 0.0, ep_chunks: int = 1, ep_native: bool = False, moe_stats: bool = False):
+        """moe_stats: every task pass's engine keeps the routing statistics of its MoE blocks (BackboneEngine moe_stats; read
+        them with `engs[j].moe_stats()` - pass j runs task tasks[j]).
+        ep_capacity (expert parallel only; 0 = the exact exchange): fixed row capacity of the exchange as a multiple of
         the uniform share R / W per (source, destination) pair (BackboneEngine ep_capacity).  The step then reads ONE flag
         on the host, at its end, instead of 2 W split sizes per MoE layer and pass, and repeats itself on the exact path
         when some pair overflowed (same gradients either way: tests/test_ep_engine_gpu.py).
@@ -62,7 +64,7 @@ class MultiTaskStep:
         self.eng = BackboneEngine(cfg, params, batch=batch, dtype=dtype, device=str(self.dev),
                                   ep_world=self.world if self.use_ep else 1, ep_rank=rank if self.use_ep else 0,
                                   wgrad_stream=wg, checkpoint=checkpoint, ep_capacity=self.ep_capacity, ep_chunks=self.ep_chunks,
-                                  ep_native=bool(ep_native) and self.use_ep)
+                                  ep_native=bool(ep_native) and self.use_ep, moe_stats=moe_stats)
         self.par = bool(parallel_tasks) and not self.use_ep and len(self.tasks) > 1
         # expert parallel: the task passes still get their own engine contexts and streams, but their blocks are
         # interleaved on the host (_ep_interleaved): each pass stops once per MoE layer to read its exchange's split
@@ -71,7 +73,7 @@ class MultiTaskStep:
         self.engs = [self.eng] + ([BackboneEngine(cfg, None, batch=batch, dtype=dtype, device=str(self.dev), share=self.eng,
                                                    ep_world=self.world if self.use_ep else 1, ep_rank=rank if self.use_ep else 0,
                                                    wgrad_stream=wg, checkpoint=checkpoint, ep_capacity=self.ep_capacity, ep_chunks=self.ep_chunks,
-                                                   ep_native=bool(ep_native) and self.use_ep)
+                                                   ep_native=bool(ep_native) and self.use_ep, moe_stats=moe_stats)
                                     for _ in self.tasks[1:]]
                                     if (self.par or self.par_ep) else [])
         # (measured and dropped in round 3, profiles/r03_stream_experiments.txt: a high-priority side stream serialises the

@@ -4,8 +4,8 @@ module names, state_dict keys and forward signatures, running on the HIP kernels
 
 Scope notes: drop / attn_drop must be 0 (as in every BASELINE config), drop_path is supported (torch-level per-sample
 scaling of the residual branches, as pretrain/configs/deit_moe_small.yaml uses it); pretrained
-weight loading, hybrid backbones, distilled tokens, wandb statistics and the sem regularisers are
-out of scope.  `forward` returns (tokens [B,N,D], total_cv_loss) like :882-886.
+weight loading, hybrid backbones, distilled tokens and the sem regularisers are out of scope (SURVEY.md section 8);
+the routing statistics the reference logs to wandb are there (`moe_stats=True`: `latest_moe_stats`, device-side, read lazily).  `forward` returns (tokens [B,N,D], total_cv_loss) like :882-886.
 
 convention="origin" (ctor flag of VisionTransformerMoE / Block, handed down to the layer and the gate) selects the API
 of models/moe/origin/* instead - what train_fastmoe.py builds with --use_checkpointing False (:425-435): the gate
@@ -21,6 +21,7 @@ import torch.nn as nn
 from .functional import AttentionCoreFn, LayerNormFn, MlpFn, PlainLinearFn
 from .gate import NoisyGate_VMoE
 from .moe_layer import FMoETransformerMLP
+from . import moe_stats as _ms
 
 
 from .balance import block_balance_loss, cv_squared, gates_to_load as _gates_to_load, prob_in_top_k as _prob_in_top_k  # noqa: E402,F401
@@ -162,12 +163,23 @@ class Block(nn.Module):
                  moe_gate_type="noisy_vmoe", vmoe_noisy_std=1, gate_task_specific_dim=-1, multi_gate=False,
                  regu_experts_fromtask=False, num_experts_pertask=-1, num_tasks=-1, gate_input_ahead=False,
                  regu_sem=False, sem_force=False, regu_subimage=False, expert_prune=False, use_checkpointing=False,
-                 convention="ckpt", site=""):
+                 convention="ckpt", site="", moe_stats=False):
+        """moe_stats (MoE blocks, convention "ckpt"; off by default): every forward leaves the block's routing statistics
+        (vision_transformer_moe.py:461-478,546-562) in a device-resident record (m3_moe_stats); `last_moe_analysis` reads it
+        on access - nothing is copied to the host inside forward."""
         super().__init__()
         assert attn_drop == 0.0, "dropout on the attention probabilities is not supported"
         assert convention in ("ckpt", "origin")
         self.convention = convention
         self.moe = moe
+        if moe_stats and moe and convention == "origin":
+            raise NotImplementedError("moe_stats=True with convention='origin': the origin layer API returns neither the "
+                                      "gates nor the clean logits (and the reference's origin backbone has no statistics)")
+        self.moe_stats = bool(moe_stats) and bool(moe)
+        self.expert_hidden_dim = None                                      # :403-405: None on dense blocks
+        self.active_vs_dense_flops_ratio = None
+        self._stats_rec = None           # the record of the last per-op forward (int32, on the device)
+        self._stats_reader = None        # set by a backbone that owns the records (fused path): () -> dict
         self.norm1 = norm_layer(dim)
         self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale, proj_drop=drop, site=site)
         self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()      # :397-398 (one module, two draws per block)
@@ -181,6 +193,8 @@ class Block(nn.Module):
                 moe_gate_dim = dim
             if moe_mlp_ratio < 0:
                 moe_mlp_ratio = mlp_ratio
+            self.expert_hidden_dim, self.active_vs_dense_flops_ratio = _ms.static_fields(dim, mlp_ratio, moe_mlp_ratio,
+                                                                                         moe_top_k)      # :417-419
             if moe_gate_type != "noisy_vmoe":
                 raise ValueError("only moe_gate_type='noisy_vmoe' works with this layer (SURVEY App. A.8)")
             self.mlp = FMoETransformerMLP(num_expert=moe_experts, d_model=dim, d_gate=moe_gate_dim,
@@ -206,9 +220,50 @@ class Block(nn.Module):
         if not self.moe:
             return x + self.drop_path(self.mlp(normed).to(x.dtype)), None
         out, clean, noisy, std, top_logits, gates = self.mlp(normed, gate_inp, task_id, task_specific_feature, sem)
+        if self.moe_stats:
+            self._record_stats(normed, out, clean, noisy, std, top_logits, gates)
         x = x + self.drop_path(self.mlp_drop(out).to(x.dtype))
         cv_loss = block_balance_loss(gates, clean, noisy, std, top_logits, self.mlp.top_k) if self.training else 0   # :453-459,540
         return x, cv_loss
+
+
+    @torch.no_grad()
+    def _record_stats(self, normed, out, clean, noisy, std, top_logits, gates):
+        """per-op path: one m3_moe_stats launch on this call's tensors.  `out` is the layer output before mlp_drop / DropPath
+        (:447-449) as the module returns it - in the activation dtype, which is what the reference's moe_output.float()
+        sees - so it is handed over as y with k = 1 and a score of one.  load: the vector of the balance loss (:456-459)."""
+        from . import ops
+        D = normed.shape[-1]
+        E = gates.shape[-1]
+        h = normed.detach().reshape(-1, D).contiguous()
+        y = out.detach().reshape(-1, D).to(h.dtype).contiguous()
+        g = gates.detach().reshape(-1, E).float().contiguous()
+        c = clean.detach().reshape(-1, E).float().contiguous()
+        if self.mlp.top_k < E and abs(std) > 1e-6:
+            load = _prob_in_top_k(c, noisy.detach().reshape(-1, E).float(), std, top_logits.detach(), self.mlp.top_k).sum(0)
+            load = load.float().contiguous()
+        else:
+            load = _gates_to_load(g).contiguous()
+        rec = torch.zeros(_ms.record_words(E), dtype=torch.int32, device=h.device)
+        ops.moe_stats(torch.ones(h.shape[0], 1, dtype=torch.float32, device=h.device), c, g, h, y, load, rec)
+        self._stats_rec = rec
+        self._stats_reader = None
+
+    def _parse_stats(self, words):
+        E = len(words) - _ms.HDR
+        return _ms.parse_record(words, E, self.expert_hidden_dim or 0, self.active_vs_dense_flops_ratio or 0.0)
+
+    @property
+    def last_moe_analysis(self):
+        """the reference's per-block dict (:552-562) of the last forward, None on a dense block, with moe_stats off or before
+        the first forward; read from the device on access"""
+        if not self.moe_stats:
+            return None
+        if self._stats_reader is not None:
+            return self._stats_reader()
+        if self._stats_rec is None:
+            return None
+        return self._parse_stats(self._stats_rec.cpu().tolist())
 
 
 class new_Mlp(nn.Module):
@@ -232,7 +287,8 @@ class VisionTransformerMoE(nn.Module):
                  gate_dim=-1, moe_gate_type="noisy_vmoe", vmoe_noisy_std=1, gate_task_specific_dim=-1,
                  multi_gate=False, regu_experts_fromtask=False, num_experts_pertask=-1, num_tasks=-1,
                  gate_input_ahead=False, expert_prune=False, use_checkpointing=False, act_dtype=torch.float32,
-                 random_init=True, sem_force=False, convention="ckpt", fused="auto", fused_grads="auto", **kwargs):
+                 random_init=True, sem_force=False, convention="ckpt", fused="auto", fused_grads="auto", moe_stats=False,
+                 **kwargs):
         """fused: "auto" (default) / True - forward(x, task_id) runs as ONE autograd node on the straight-line executor
         (m3vit_amd/fused.py: hipGraph replay, the parameters' .grad are views of its flat gradient buffer) whenever the call
         is one it covers, and through the per-op autograd Functions below otherwise (`fused_fallback_reason` says why);
@@ -243,8 +299,19 @@ class VisionTransformerMoE(nn.Module):
         copy per backward call), so all of those work as on the per-op path.  "auto" (default) - "autograd" inside the
         forward of a torch DistributedDataParallel that wraps this model or when a trainable parameter carries a tensor hook
         or post-accumulate-grad hook, "views" otherwise.  `fused_grads_used` records what the last call used (None when it
-        did not run on the executor with autograd on)."""
+        did not run on the executor with autograd on).
+        moe_stats (off by default; with it off nothing below exists and `latest_moe_stats` is None): every forward leaves the
+        routing statistics of its MoE blocks in device-resident records (m3_moe_stats; on the fused path inside the captured
+        pass).  `latest_moe_stats` - the reference's dict (:799-873) for the most recent forward call - and every MoE
+        block's `last_moe_analysis` copy them to the host when they are READ, never inside forward.  `wandb_logger`
+        (None by default, :693-696): set it to a callable; a training-mode forward then calls
+        `wandb_logger().log_moe_stats(stats)` when it returns a logger (:875-878) - that reads the records on the host
+        every step, by the caller's choice."""
         super().__init__()
+        self.moe_stats = bool(moe_stats)
+        self.wandb_logger = None
+        self._stats_src = None           # which path ran the most recent forward call: "fused" | "perop"
+        self._stats_cache = None
         assert convention in ("ckpt", "origin")
         assert fused_grads in ("auto", "views", "autograd"), f"fused_grads={fused_grads!r}: 'auto', 'views' or 'autograd'"
         self.convention = convention
@@ -315,7 +382,7 @@ class VisionTransformerMoE(nn.Module):
                                     multi_gate=multi_gate, regu_experts_fromtask=regu_experts_fromtask,
                                     num_experts_pertask=num_experts_pertask, num_tasks=num_tasks,
                                     gate_input_ahead=gate_input_ahead, expert_prune=expert_prune,
-                                    sem_force=sem_force, convention=convention))
+                                    sem_force=sem_force, convention=convention, moe_stats=moe_stats))
         self.blocks = nn.Sequential(*blocks)
         self.pre_logits = nn.Identity()
         self.init_weights()
@@ -386,7 +453,50 @@ class VisionTransformerMoE(nn.Module):
         return x, total_cv
 
     def forward(self, x, gate_inp=None, task_id=None, sem=None):
-        return self.forward_features(x, gate_inp, task_id=task_id, sem=sem)
+        out = self.forward_features(x, gate_inp, task_id=task_id, sem=sem)
+        if self.moe_stats:
+            self._stats_src = "fused" if self.fused_fallback_reason is None and self.fused else "perop"
+            self._stats_cache = None
+            if self._stats_src == "fused":
+                for i, blk in enumerate(self.blocks):
+                    if blk.moe:
+                        blk._stats_reader = partial(self._block_stats, i)
+            if self.training and self.wandb_logger is not None:            # :875-878
+                logger = self.wandb_logger()
+                if logger is not None:
+                    stats = self.latest_moe_stats
+                    if stats is not None and stats["moe_blocks"] > 0:
+                        logger.log_moe_stats(stats)
+        return out
+
+    def _read_stats(self):
+        """(block dicts by block index, backbone dict) of the most recent forward call; one device-to-host copy, cached until
+        the next forward"""
+        if self._stats_cache is None and self._stats_src is not None:
+            if self._stats_src == "fused":
+                self._stats_cache = self._fused.read_moe_stats() if self._fused is not None else None
+            else:
+                moe = [(i, blk) for i, blk in enumerate(self.blocks) if blk.moe and blk._stats_rec is not None]
+                if moe:
+                    rows = torch.stack([blk._stats_rec for _, blk in moe]).cpu().tolist()
+                    blocks = {i: blk._parse_stats(r) for (i, blk), r in zip(moe, rows)}
+                    N = self.num_patches + 1
+                    B = blocks[moe[0][0]]["gate_token_count"] // N
+                    self._stats_cache = (blocks, _ms.aggregate([blocks[i] for i in sorted(blocks)], B * max(N - 1, 0)))
+        return self._stats_cache
+
+    def _block_stats(self, i):
+        got = self._read_stats()
+        return None if got is None else got[0].get(i)
+
+    @property
+    def latest_moe_stats(self):
+        """{"moe_blocks", "total_positions", "analysis": {...}} of the most recent forward call (:799-873); None with
+        moe_stats off or before the first forward.  The records are copied from the device here, not in forward."""
+        if not self.moe_stats:
+            return None
+        got = self._read_stats()
+        return None if got is None else got[1]
 
 
 def _make_norm(dim, act_dtype=torch.float32):
