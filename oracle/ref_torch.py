@@ -27,7 +27,8 @@ __all__ = [
 # --------------------------------------------------------------------------- gate
 def gate_vmoe(x: torch.Tensor, w_gate: torch.Tensor, top_k: int,
               noise: Optional[torch.Tensor] = None, noise_std: float = 0.0,
-              training: bool = True, idx_override: Optional[torch.Tensor] = None):
+              training: bool = True, idx_override: Optional[torch.Tensor] = None,
+              logit_bias: Optional[torch.Tensor] = None):
     """NoisyGate_VMoE.forward, models/moe/ckpt/noisy_gate_vmoe.py:80-264
     (torch-only twin models/moe/gates.py:405-466).
 
@@ -41,10 +42,14 @@ def gate_vmoe(x: torch.Tensor, w_gate: torch.Tensor, top_k: int,
     idx_override (test aid, not in the reference): use these expert indices instead of the top-k and
     take their scores from the same softmax - lets a reduced-precision run be checked value-for-value
     on ITS OWN routing once that routing has been verified separately on its own gate input.
+    logit_bias (test aid, not in the reference): [E], added to every token's clean logits - what the columns
+    cat(inp, tsf) @ w_gate[D:] of a task-conditioned gate add, supplied by the caller (the engine's tsf_bias).
     """
     x2 = x.reshape(-1, x.shape[-1])
     E = w_gate.shape[1]
     clean = x2 @ w_gate
+    if logit_bias is not None:
+        clean = clean + logit_bias.to(clean.dtype)
     std = (noise_std / E) * (1.0 if training else 0.0)
     if noise is not None and std != 0.0:
         noisy = clean + noise * std
@@ -170,7 +175,7 @@ def moe_dispatch_ffn(x: torch.Tensor, idx: torch.Tensor, w1, b1, w2, b2):
 
 
 def moe_layer(x: torch.Tensor, gate_x: torch.Tensor, w_gate, w1, b1, w2, b2, top_k: int,
-              noise=None, noise_std: float = 0.0, training: bool = True, idx_override=None):
+              noise=None, noise_std: float = 0.0, training: bool = True, idx_override=None, logit_bias=None):
     """FMoETransformerMLP.forward / forward_moe, models/moe/ckpt/custom_moe_layer.py:161-322
     (gate :213-219, dispatch :263-265, combine bmm(score[T,1,k], out[T,k,D]) :291-305).
     gate_x is the gate input ([T,D] or [T,D+gtsd] after the task-conditioning cat :176-179).
@@ -178,7 +183,7 @@ def moe_layer(x: torch.Tensor, gate_x: torch.Tensor, w_gate, w1, b1, w2, b2, top
     shp = x.shape
     x2 = x.reshape(-1, shp[-1])
     (idx, score), clean, noisy, std, top_logits, gates = gate_vmoe(
-        gate_x, w_gate, top_k, noise, noise_std, training, idx_override)
+        gate_x, w_gate, top_k, noise, noise_std, training, idx_override, logit_bias)
     y = moe_dispatch_ffn(x2, idx, w1, b1, w2, b2)            # [T*k, D]
     y = y.view(-1, top_k, y.shape[-1])
     out = torch.bmm(score.view(-1, 1, top_k), y).reshape(-1, y.shape[-1])
@@ -329,10 +334,11 @@ def patch_embed(images, w, b, cls_token, pos_embed):
 
 
 def block_forward(params, cfg: BackboneCfg, i: int, x, task_id: Optional[int], tsf=None,
-                  training: bool = True, noise=None, idx_override=None, path_scale=None):
+                  training: bool = True, noise=None, idx_override=None, path_scale=None, logit_bias=None):
     """Block._ckpt_main_moe / _ckpt_non_moe, vision_transformer_moe.py:438-487, and the
     cv-loss part of Block.forward :539-543 (mlp_drop = 0).  path_scale: None (drop_path = 0) or the two per-sample
     factors DropPath (:167-185) multiplies the attention and the MLP / MoE branch with: mask / keep_prob, each [B].
+    logit_bias: None or [E], added to the gate's clean logits (gate_vmoe).
     Returns (x_out, cv_loss or None, aux dict)."""
     p = params
     b = f"blocks.{i}."
@@ -363,7 +369,7 @@ def block_forward(params, cfg: BackboneCfg, i: int, x, task_id: Optional[int], t
         p[b + "mlp.experts.htoh4.weight"], p[b + "mlp.experts.htoh4.bias"],
         p[b + "mlp.experts.h4toh.weight"], p[b + "mlp.experts.h4toh.bias"],
         cfg.moe_top_k, noise=noise, noise_std=cfg.vmoe_noisy_std, training=training,
-        idx_override=idx_override)
+        idx_override=idx_override, logit_bias=logit_bias)
     x = x + s_mlp * _drop("mlp_drop", out)
     importance = gates.sum(0)                                  # :453
     E = gates.shape[1]
@@ -377,19 +383,20 @@ def block_forward(params, cfg: BackboneCfg, i: int, x, task_id: Optional[int], t
 
 
 def backbone_forward(params, cfg: BackboneCfg, images, task_id: Optional[int], training: bool = True,
-                     noises=None, route_override=None, path_scales=None, dropout=None):
+                     noises=None, route_override=None, path_scales=None, dropout=None, logit_bias=None):
     """VisionTransformerMoE.forward_features, vision_transformer_moe.py:780-880:
     returns (tokens[B,N,D] of the last block, total_cv_loss).  dropout: fn(site, tensor) -> tensor applied at the
-    element-wise dropout sites (see _DROP above)."""
+    element-wise dropout sites (see _DROP above).  logit_bias: {block: [E]} added to that block's gate logits (the
+    engine's tsf_bias / MultiTaskStep.bind(logit_bias=): routing-skew tests)."""
     p = params
     _DROP["fn"], _DROP["prefix"] = dropout, ""
     try:
-        return _backbone_forward(p, cfg, images, task_id, training, noises, route_override, path_scales)
+        return _backbone_forward(p, cfg, images, task_id, training, noises, route_override, path_scales, logit_bias)
     finally:
         _DROP["fn"], _DROP["prefix"] = None, ""
 
 
-def _backbone_forward(p, cfg, images, task_id, training, noises, route_override, path_scales):
+def _backbone_forward(p, cfg, images, task_id, training, noises, route_override, path_scales, logit_bias=None):
     x = patch_embed(images, p["patch_embed.proj.weight"], p["patch_embed.proj.bias"],
                     p["cls_token"], p["pos_embed"])
     x = _drop("pos", x)
@@ -402,7 +409,8 @@ def _backbone_forward(p, cfg, images, task_id, training, noises, route_override,
         noise = None if noises is None else noises.get(i)
         ovr = None if route_override is None else route_override.get(i)
         ps = None if path_scales is None else path_scales.get(i)
-        x, cv, aux = block_forward(p, cfg, i, x, task_id, tsf, training, noise, ovr, ps)
+        lb = None if logit_bias is None else logit_bias.get(i)
+        x, cv, aux = block_forward(p, cfg, i, x, task_id, tsf, training, noise, ovr, ps, lb)
         if cv is not None:
             total_cv = total_cv + cv
         aux_all.append(aux)

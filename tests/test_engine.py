@@ -360,7 +360,10 @@ def test_split_backward_and_gradient_slices():
 
 def test_multitask_step_runner_graph_and_streams_match_serial():
     """m3vit_amd.step.MultiTaskStep (what bench.py drives): task passes on their own streams inside a replayed
-    hipGraph give the gradients of the serial reference order, step after step."""
+    hipGraph give the gradients of the serial reference order, step after step.  (The noisy / skewed half below replays
+    the SAME bound inputs and compares the runner with itself; the runner against the float64 oracle under noise and a logit
+    bias, with new inputs written into the bound tensors between replays and every buffer poisoned before each step:
+    tests/test_engine_stale_state_gpu.py.)"""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     from m3vit_amd.step import MultiTaskStep
