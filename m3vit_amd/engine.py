@@ -25,30 +25,24 @@ from typing import Dict, Optional
 
 import torch
 
-import os
-
 from . import moe_stats as _ms
 from . import ops
+from .engine_ep import ExpertParallelMixin
 from .ops import M3_ACT_GELU
 
-_ROUTE_FOLD = os.environ.get("M3_ROUTE_FOLD", "1") != "0"       # A/B knob: 0 = the three-launch m3_route_build behind the gate
+
+def _cut(t, es):
+    return t if es is None else t[es]
 
 
-class _Cfg:
-    """Duck-typed config: any object with the attribute names of oracle.BackboneCfg /
-    the VisionTransformerMoE ctor works (img_size, patch_size, in_chans, embed_dim, depth,
-    num_heads, mlp_ratio, moe_mlp_ratio, moe_experts, moe_top_k, gate_dim, multi_gate,
-    gate_task_specific_dim, vmoe_noisy_std)."""
-
-
-class BackboneEngine:
+class BackboneEngine(ExpertParallelMixin):
     def __init__(self, cfg, params: Dict[str, torch.Tensor], batch: int, dtype=torch.float16,
                  device="cuda:0", ep_group=None, ep_world: int = 1, ep_rank: int = 0, share: "BackboneEngine" = None,
                  wgrad_stream: bool = False, checkpoint: bool = False, ep_capacity: float = 0.0,
                  experts_are_local: bool = False, ep_chunks: int = 1, ep_native: bool = False, moe_stats: bool = False):
         """params: GLOBAL parameters (all E experts).  With ep_world > 1 this rank keeps experts
         [ep_rank*E/W, (ep_rank+1)*E/W) (utils/common_config.py:179-185) and exchanges routed rows with
-        the other ranks over torch.distributed (RCCL) - see _experts_fwd_ep.
+        the other ranks over torch.distributed (RCCL) - see engine_ep._experts_fwd_ep.
         share: another engine of the same configuration whose parameters and operand copies this one
         uses (params is ignored); it gets its own activations, scratch and gradient buffer, so the two
         can run different task passes concurrently on different HIP streams.
@@ -70,7 +64,7 @@ class BackboneEngine:
         (MultiTaskStep does).
         ep_chunks (with ep_world > 1, exact exchange; 1 = one all-to-all-v each way): cut every exchange into this many
         chunks of E_loc / ep_chunks local experts (on every destination) and overlap them with the experts' GEMMs inside ONE
-        pass - see _experts_fwd_ep_chunked.  Same results bit for bit.
+        pass - see engine_ep._experts_fwd_ep_chunked.  Same results bit for bit.
         ep_native (with ep_world > 1; opt-in, never run on more than one rank on this build box): the count and row exchanges
         go through the library's own RCCL entry points (m3vit_amd/ep_native.py: m3_ep_exchange_counts / m3_ep_dispatch /
         m3_ep_return) instead of torch.distributed's all_to_all_single.
@@ -246,8 +240,9 @@ class BackboneEngine:
         shapes = [(T, self.Hd, D, 1), (T, D, self.Hd, 1), (T, 3 * D, D, 1), (T, D, D, 1),
                   (R, self.Hm, D, self.E), (R, D, self.Hm, self.E), (self.B * self.np_, D, Kp, 1), (T, D, self.E, 1)]
         if self.ep_capacity:                                   # the padded exchange contracts over the capacity bound
-            ncap = self.ep_world * ((-(-int(self.ep_capacity * R + self.ep_world - 1) // self.ep_world) + 7) // 8 * 8)
-            shapes += [(ncap, self.Hm, D, self.E_loc), (ncap, D, self.Hm, self.E_loc)]
+            W = self.ep_world
+            self.ep_cap = (-(-int(self.ep_capacity * R + W - 1) // W) + 7) // 8 * 8        # rows per (source, destination) pair
+            shapes += [(W * self.ep_cap, self.Hm, D, self.E_loc), (W * self.ep_cap, D, self.Hm, self.E_loc)]
         for (M, N, K, G) in shapes:
             wg = max(wg, ops.wgrad_ws_elems(M, N, K, G, grouped=G > 1, dtype=self.dt))
         # weight-gradient slab reductions ride in front of the NEXT weight-gradient launch of the pass (ops.WgradQueue: two
@@ -285,38 +280,7 @@ class BackboneEngine:
             self.stats_rec = torch.zeros(len(self.stats_row), _ms.record_words(self.E), dtype=torch.int32, device=self.dev)
             self.ws_stats = self._e(ops.moe_stats_ws_elems(T, self.E), dtype=f32)
         if self.ep_world > 1:
-            # expert-parallel exchange plans: one regroup index per MoE block (kept for the backward; a rank can
-            # receive at most what all ranks route) and the pinned landing buffer of the split sizes
-            self.ep_regroup = {i: torch.empty(self.ep_world * R, dtype=torch.int32, device=self.dev)
-                               for i in range(self.depth) if self.is_moe[i]}
-            self.ep_splits_host = torch.empty(2 * self.ep_world, dtype=torch.int64, pin_memory=True)
-            if self.ep_chunks > 1:
-                # chunked exchange: rows are routed by a CHUNK-MAJOR key - (chunk of the local expert, destination rank,
-                # expert inside the chunk) - so that what goes to every rank for one chunk of its experts is one
-                # contiguous run of the send buffer, in destination order (one all_to_all_single per chunk)
-                C, W, Ec = self.ep_chunks, self.ep_world, self.E_loc // self.ep_chunks
-                e = torch.arange(self.E)
-                d_, rest = e // self.E_loc, e % self.E_loc
-                self.ep_key = ((rest // Ec) * (W * Ec) + d_ * Ec + rest % Ec).to(torch.int32).to(self.dev)
-                self.ep_regroup_c = {i: torch.empty(C, W * R, dtype=torch.int32, device=self.dev)
-                                     for i in range(self.depth) if self.is_moe[i]}
-                self.ep_splits_host_c = torch.empty(C, 2 * W, dtype=torch.int64, pin_memory=True)
-            if self.ep_capacity:
-                W = self.ep_world
-                self.ep_cap = -(-int(self.ep_capacity * R + W - 1) // W)                # rows per (source, destination) pair
-                self.ep_cap = (self.ep_cap + 7) // 8 * 8
-                self.ep_overflow = torch.zeros(1, dtype=torch.int32, device=self.dev)
-                n = W * self.ep_cap
-                # static buffers of the padded exchange, per MoE block (a captured step replays on fixed addresses)
-                # (zeroed once: the rows of a pair's share that no routed row fills travel over the wire as they are - never read
-                # back, unpad_idx does not select them, but they should not be whatever the allocator left there)
-                z = lambda *shape: torch.zeros(*shape, dtype=self.dt, device=self.dev)                   # noqa: E731
-                self.ep_fx = {i: dict(x_send=z(n, D), x_recv=z(n, D), hid_pre=z(n, self.Hm),
-                                      hid=z(n, self.Hm), y_recv=z(n, D), y_back=z(n, D),
-                                      recv_counts=torch.zeros(self.E, dtype=torch.int64, device=self.dev), plan=None)
-                              for i in range(self.depth) if self.is_moe[i]}
-                self.ep_fx_bwd = dict(dy_send=z(n, D), dy_recv=z(n, D), dhp=z(n, self.Hm),
-                                      dx_recv=z(n, D), dx_back=z(n, D))
+            self._alloc_ep()
 
     def cfg_d_gate(self):
         g = self.cfg.gate_task_specific_dim
@@ -435,6 +399,43 @@ class BackboneEngine:
                 self.grads[n] += g
         self._tsf = None
 
+    # The expert FFN of MoE block i - the ONE place its launches are stated.  Slot m of M (expert-major; `offsets` / `tiles`:
+    # the group offsets and tile prefix) stands for row idx[m] // div of x / d y and row idx[m] of y / d x: local experts pass
+    # (row_of_slot, k), the expert-parallel exchanges (engine_ep.py) their regroup index with div 1.  es: the experts the
+    # GEMMs run on (the chunked exchange: one chunk of the local experts).
+    def _ffn_fwd(self, i, x, hid_pre, hid, y, M, idx, div, offsets, tiles, es=None):
+        """grouped FC1 (+bias+GELU, rows of x gathered through idx) -> hid_pre, hid; grouped FC2 (+bias, rows scattered
+        through idx) -> y.  y None: FC1 only (the checkpoint recompute under expert parallelism)."""
+        fc1, fc2, p = f"blocks.{i}.mlp.experts.htoh4", f"blocks.{i}.mlp.experts.h4toh", self.params
+        ops.gemm_nt(x, _cut(self.wc[fc1], es), hid, M=M, bias=_cut(p[fc1 + ".bias"], es), act=M3_ACT_GELU, pre_out=hid_pre,
+                    a_row_idx=idx, a_row_div=div, group_offsets=offsets, tile_starts=tiles)
+        if y is not None:
+            ops.gemm_nt(hid, _cut(self.wc[fc2], es), y, M=M, bias=_cut(p[fc2 + ".bias"], es), c_row_idx=idx,
+                        group_offsets=offsets, tile_starts=tiles)
+
+    def _ffn_bwd(self, i, dy, x, hid_pre, hid, dhp, dx, M, idx, div, offsets, tiles, es=None, score=None,
+                 dgrad=True, wgrad=True):
+        """mirror of _ffn_fwd: FC2 weight gradient, FC2 input gradient (d y -> dhp), FC1 weight gradient, FC1 input gradient
+        (dhp -> dx, rows scattered through idx), in this order.  score (local experts): slot m's row of d y is score[idx[m]]
+        times the row read - the combine's backward folded in (see backward_blocks).  dgrad / wgrad False leave that half out
+        (the chunked exchange: input gradients per chunk, weight gradients once over all local experts, es not applied).
+        The reads= tags and _before_write order the weight-gradient side stream (no-ops without one)."""
+        fc1, fc2 = f"blocks.{i}.mlp.experts.htoh4", f"blocks.{i}.mlp.experts.h4toh"
+        assert es is None or not wgrad
+        if wgrad:
+            self._wgrad(dy, hid, fc2 + ".weight", M=M, c_row_idx=idx, c_row_div=div, c_row_scale=score,
+                        group_offsets=offsets, bias=fc2 + ".bias", reads=("dx_t",))
+        if dgrad:
+            self._before_write("dpre")
+            ops.gemm_nt(dy, _cut(self.wt[fc2], es), dhp, M=M, gelu_grad_pre=hid_pre, a_row_idx=idx, a_row_div=div,
+                        row_scale=score, row_scale_idx=idx if score is not None else None, group_offsets=offsets,
+                        tile_starts=tiles)
+        if wgrad:
+            self._wgrad(dhp, x, fc1 + ".weight", M=M, a_row_idx=idx, a_row_div=div, group_offsets=offsets,
+                        bias=fc1 + ".bias", reads=("dpre",))
+        if dgrad:
+            ops.gemm_nt(dhp, _cut(self.wt[fc1], es), dx, M=M, c_row_idx=idx, group_offsets=offsets, tile_starts=tiles)
+
     def _block_forward(self, i, x, loss_acc):
         """block i on residual stream x -> its output buffer (vision_transformer_moe.py:438-562: pre-LN attention +
         MLP / MoE branch).  Called by forward() and, in checkpoint mode, again by backward_blocks() right before the
@@ -470,20 +471,14 @@ class BackboneEngine:
             # gate + balance loss (importance, load, cv^2 and its gradient) + dispatch metadata: three launches (the routing
             # histogram comes out of the gate kernel, its scan rides in the balance launch)
             g = ops.gate_fwd(a["h2"], wg_tok, self.k, logit_bias=None if tsf_bias is None else tsf_bias[i],
-                             noise=noise, noise_std=std, dense=True, loss_acc=loss_acc, route=self.ep_world == 1 and _ROUTE_FOLD)
+                             noise=noise, noise_std=std, dense=True, loss_acc=loss_acc, route=self.ep_world == 1)
             a["gate"] = g
             if self.ep_world > 1:
                 self._experts_fwd_ep(i, a, g, recompute=loss_acc is None)
             else:
-                r = g["route"] if g["route"] is not None else ops.route_build(g["idx32"], self.E)
+                r = g["route"] if g["route"] is not None else ops.route_build(g["idx32"], self.E)     # (None when 16 % k != 0)
                 a["route"] = r
-                ops.gemm_nt(a["h2"], self.wc[b + "mlp.experts.htoh4"], a["hid"], M=self.R,
-                            bias=p[b + "mlp.experts.htoh4.bias"], act=M3_ACT_GELU, pre_out=a["hid_pre"],
-                            a_row_idx=r.row_of_slot, a_row_div=self.k, group_offsets=r.offsets,
-                            tile_starts=r.tile_starts)
-                ops.gemm_nt(a["hid"], self.wc[b + "mlp.experts.h4toh"], a["y"], M=self.R,
-                            bias=p[b + "mlp.experts.h4toh.bias"], c_row_idx=r.row_of_slot,
-                            group_offsets=r.offsets, tile_starts=r.tile_starts)
+                self._ffn_fwd(i, a["h2"], a["hid_pre"], a["hid"], a["y"], self.R, r.row_of_slot, self.k, r.offsets, r.tile_starts)
             if sm is not None:                          # out = x1 + scale[sample] * sum_j score_j y_j
                 a["sm_tok"] = sm.view(B, 1).expand(B, N).reshape(T, 1).contiguous()
                 a["score_s"] = g["score"] * a["sm_tok"]
@@ -560,279 +555,6 @@ class BackboneEngine:
     def forward_end(self, x):
         # total cv_loss = sum over MoE blocks of cv^2(importance) + cv^2(load)  (vision_transformer_moe.py:453-459,540)
         return x.view(self.B, self.N, self.D), self.cv_acc[0].clone()
-
-    # ------------------------------------------------------------- expert parallel
-    def _a2a(self, x, in_splits, out_splits):
-        import torch.distributed as dist
-        out = torch.empty((sum(out_splits),) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
-        if self.ep_native is not None:
-            self.ep_native.dispatch_async(out, x.contiguous(), out_splits, in_splits).wait()
-            return out
-        dist.all_to_all_single(out, x.contiguous(), output_split_sizes=out_splits, input_split_sizes=in_splits,
-                               group=self.ep_group)
-        return out
-
-    def _experts_fwd_ep(self, i, a, g, recompute=False):
-        """EP forward of one MoE layer: ONE count exchange + ONE row exchange each way (m3vit_amd/ep.py has
-        the same logic for the module API).  Rows are routed by GLOBAL expert id, so the expert-major send
-        buffer is already grouped by destination rank; received rows are regrouped from (src, expert) to
-        (expert, src) order for the local grouped GEMMs.
-        recompute (checkpoint mode, called from backward_blocks): the gate has just been re-run on the same input, so the
-        routing is the forward's; the plan, the received rows and the returned outputs a["y"] were kept - only FC1 of the
-        local experts is run again (its hidden activations are what the backward needs), no collective."""
-        import torch.distributed as dist
-        b = f"blocks.{i}."
-        p, k, D, dev = self.params, self.k, self.D, self.dev
-        if self.ep_fixed:
-            return self._experts_fwd_ep_fixed(i, a, g)
-        if self.ep_chunks > 1 and not recompute:
-            return self._experts_fwd_ep_chunked(i, a, g)
-        if recompute:
-            ep = a["ep"]
-            n = ep["n"]
-            if n > 0:
-                ep["hid_pre"], ep["hid"] = self._e(n, self.Hm), self._e(n, self.Hm)
-                ops.gemm_nt(ep["x_recv"], self.wc[b + "mlp.experts.htoh4"], ep["hid"], M=n,
-                            bias=p[b + "mlp.experts.htoh4.bias"], act=M3_ACT_GELU, pre_out=ep["hid_pre"],
-                            a_row_idx=ep["rg"], a_row_div=1, group_offsets=ep["offsets"], tile_starts=ep["tile_starts"])
-            return
-        r = ops.route_build(g["idx32"], self.E, want_counts64=True)
-        a["route"] = r
-        x_send = self._e(self.R, D)
-        ops.gather_rows(a["h2"], r.row_of_slot, x_send, div=k)
-        if self.ep_native is not None:
-            recv = self.ep_native.exchange_counts(r.counts64)
-        else:
-            recv = torch.empty_like(r.counts64)
-            dist.all_to_all_single(recv, r.counts64, group=self.ep_group)
-        # the plan (regroup index, expert-major offsets, tile prefix) is built on the device; the host reads the
-        # 2 W split sizes the a2a-v API needs and nothing else
-        plan = ops.ep_plan(r.counts64, recv, self.ep_world, self.E_loc, self.ep_regroup[i], splits_host=self.ep_splits_host)
-        n = plan.n_recv
-        x_recv = self._a2a(x_send, plan.in_splits, plan.out_splits)
-        ep = dict(plan=plan, n=n, rg=plan.regroup, offsets=plan.offsets, tile_starts=plan.tile_starts)
-        y_recv = self._e(n, D)
-        ep["x_recv"] = x_recv
-        if n > 0:
-            # the (src, expert) -> (expert, src) regroup is the A-row gather of FC1 and the C-row scatter of FC2:
-            # expert-major slot i reads x_recv[rg[i]] and writes y_recv[rg[i]] - no regrouped copies
-            ep["hid_pre"], ep["hid"] = self._e(n, self.Hm), self._e(n, self.Hm)
-            ops.gemm_nt(x_recv, self.wc[b + "mlp.experts.htoh4"], ep["hid"], M=n,
-                        bias=p[b + "mlp.experts.htoh4.bias"], act=M3_ACT_GELU, pre_out=ep["hid_pre"],
-                        a_row_idx=ep["rg"], a_row_div=1, group_offsets=ep["offsets"], tile_starts=ep["tile_starts"])
-            ops.gemm_nt(ep["hid"], self.wc[b + "mlp.experts.h4toh"], y_recv, M=n, bias=p[b + "mlp.experts.h4toh.bias"],
-                        c_row_idx=ep["rg"], group_offsets=ep["offsets"], tile_starts=ep["tile_starts"])
-        y_send = self._a2a(y_recv, plan.out_splits, plan.in_splits)
-        ops.gather_rows(y_send, r.pos, a["y"])                       # back to token-major [T*k, D]
-        if self.checkpoint:                                          # local hidden activations: recomputed in backward
-            ep["hid_pre"] = ep["hid"] = None
-        a["ep"] = ep
-
-    # ------------------------------------------------------------------ expert parallel, exchange overlapped inside ONE pass
-    def _a2a_async(self, out, x, out_splits, in_splits):
-        import torch.distributed as dist
-        if self.ep_native is not None:
-            return self.ep_native.dispatch_async(out, x, out_splits, in_splits)
-        return dist.all_to_all_single(out, x, output_split_sizes=out_splits, input_split_sizes=in_splits, group=self.ep_group,
-                                      async_op=True)
-
-    def _experts_fwd_ep_chunked(self, i, a, g):
-        """_experts_fwd_ep with every exchange cut into ep_chunks all-to-all-v's, chunk c = the rows for local experts
-        [c E_loc / C, (c + 1) E_loc / C) of EVERY rank (custom_moe_layer.py:263-265): all chunks' row
-        exchanges are queued on the collective library's stream at once; the grouped FC1 / FC2 of chunk c start when ITS rows
-        have arrived - the later chunks are still in flight - and its outputs start their way home under the next chunk's GEMMs.
-        Exposed per direction: one chunk's exchange instead of the whole.  The count exchange and the plans (C m3_ep_plan
-        launches, ONE host read of the C * 2 W split sizes) are as before.  What the backward and a checkpoint recompute need
-        is kept in the unchunked form - one received buffer (the chunks side by side), one regroup index, offsets and tile
-        prefix over all local experts - so every row keeps its expert-major position and the results are bit-identical to the
-        one-exchange path."""
-        import torch.distributed as dist
-        b = f"blocks.{i}."
-        p, k, D, dev = self.params, self.k, self.D, self.dev
-        C, W = self.ep_chunks, self.ep_world
-        Ec = self.E_loc // C
-        key = self.ep_key[g["idx32"].reshape(-1).long()].view(-1, k).contiguous()          # chunk-major routing keys
-        r = ops.route_build(key, self.E, want_counts64=True)
-        a["route"] = r
-        x_send = self._e(self.R, D)
-        ops.gather_rows(a["h2"], r.row_of_slot, x_send, div=k)
-        send = r.counts64.view(C, W, Ec)
-        snd_dm = send.permute(1, 0, 2).contiguous()                                         # destination-major for the count exchange
-        if self.ep_native is not None:
-            rcv_dm = self.ep_native.exchange_counts(snd_dm.view(-1)).view_as(snd_dm)
-        else:
-            rcv_dm = torch.empty_like(snd_dm)
-            dist.all_to_all_single(rcv_dm.view(-1), snd_dm.view(-1), group=self.ep_group)
-        recv = rcv_dm.permute(1, 0, 2).contiguous()                                         # [C][source][expert of the chunk]
-        plans = ops.ep_plan_chunks(send.contiguous(), recv, W, Ec, self.ep_regroup_c[i], self.ep_splits_host_c)
-        ns = [sum(pl.in_splits) for pl in plans]
-        nr = [pl.n_recv for pl in plans]
-        sb = [sum(ns[:c]) for c in range(C + 1)]
-        rb = [sum(nr[:c]) for c in range(C + 1)]
-        n = rb[C]
-        x_recv, y_recv = self._e(n, D), self._e(n, D)
-        hid_pre, hid = self._e(n, self.Hm), self._e(n, self.Hm)
-        y_send = self._e(self.R, D)
-        works = [self._a2a_async(x_recv[rb[c]:rb[c + 1]], x_send[sb[c]:sb[c + 1]], plans[c].out_splits, plans[c].in_splits)
-                 for c in range(C)]
-        back = []
-        w1, b1 = self.wc[b + "mlp.experts.htoh4"], p[b + "mlp.experts.htoh4.bias"]
-        w2, b2 = self.wc[b + "mlp.experts.h4toh"], p[b + "mlp.experts.h4toh.bias"]
-        for c in range(C):
-            works[c].wait()
-            pl, es = plans[c], slice(c * Ec, (c + 1) * Ec)
-            if nr[c] > 0:
-                ops.gemm_nt(x_recv[rb[c]:rb[c + 1]], w1[es], hid[rb[c]:rb[c + 1]], M=nr[c], bias=b1[es], act=M3_ACT_GELU,
-                            pre_out=hid_pre[rb[c]:rb[c + 1]], a_row_idx=pl.regroup, a_row_div=1, group_offsets=pl.offsets,
-                            tile_starts=pl.tile_starts)
-                ops.gemm_nt(hid[rb[c]:rb[c + 1]], w2[es], y_recv[rb[c]:rb[c + 1]], M=nr[c], bias=b2[es], c_row_idx=pl.regroup,
-                            group_offsets=pl.offsets, tile_starts=pl.tile_starts)
-            back.append(self._a2a_async(y_send[sb[c]:sb[c + 1]], y_recv[rb[c]:rb[c + 1]], pl.in_splits, pl.out_splits))
-        # the unchunked view of the plan for the backward / a checkpoint recompute: chunk c's rows sit at rb[c] of the received
-        # buffer and its experts at c * Ec of the local experts
-        rg = torch.cat([plans[c].regroup + rb[c] for c in range(C)]) if n else self.ep_regroup_c[i][0, :0]
-        offs = torch.cat([plans[c].offsets[:-1] + rb[c] for c in range(C)] +
-                         [torch.full((1,), n, dtype=torch.int32, device=dev)])
-        tb = [0]
-        tsc = [plans[c].tile_starts for c in range(C)]
-        ts_all, base_t = [], torch.zeros((), dtype=torch.int32, device=dev)
-        for c in range(C):
-            ts_all.append(tsc[c][:-1] + base_t)
-            base_t = base_t + tsc[c][-1]
-        ts_all.append(base_t.reshape(1))
-        ep = dict(plan=None, chunked=True, plans=plans, sb=sb, rb=rb, n=n, rg=rg.contiguous(), offsets=offs.contiguous(),
-                  tile_starts=torch.cat(ts_all).contiguous(), x_recv=x_recv, hid_pre=hid_pre, hid=hid)
-        for w_ in back:
-            w_.wait()
-        ops.gather_rows(y_send, r.pos, a["y"])                       # back to token-major [T*k, D]
-        if self.checkpoint:                                          # local hidden activations: recomputed in backward
-            ep["hid_pre"] = ep["hid"] = None
-        a["ep"] = ep
-
-    def _experts_bwd_ep_chunked(self, i, a):
-        """mirror of _experts_fwd_ep_chunked: the d y rows travel in the same chunks; chunk c's input-gradient GEMMs run while the
-        later chunks are in flight and its d x rows go home under the next chunk's GEMMs; the weight gradients (all local
-        experts at once, on the side-by-side buffers - the same launches as the one-exchange path) run last, under the
-        returning exchanges."""
-        b = f"blocks.{i}."
-        D, r, ep = self.D, a["route"], a["ep"]
-        C, Ec = self.ep_chunks, self.E_loc // self.ep_chunks
-        plans, sb, rb, n = ep["plans"], ep["sb"], ep["rb"], ep["n"]
-        dy_send = ops.gather_rows(self.s_dy, r.row_of_slot, self._e(self.R, D))
-        dy_recv, dx_recv, dhp = self._e(n, D), self._e(n, D), self._e(n, self.Hm)
-        dx_send = self._e(self.R, D)
-        works = [self._a2a_async(dy_recv[rb[c]:rb[c + 1]], dy_send[sb[c]:sb[c + 1]], plans[c].out_splits, plans[c].in_splits)
-                 for c in range(C)]
-        back = []
-        wt2, wt1 = self.wt[b + "mlp.experts.h4toh"], self.wt[b + "mlp.experts.htoh4"]
-        for c in range(C):
-            works[c].wait()
-            pl, es = plans[c], slice(c * Ec, (c + 1) * Ec)
-            rows = slice(rb[c], rb[c + 1])
-            if rb[c + 1] > rb[c]:
-                ops.gemm_nt(dy_recv[rows], wt2[es], dhp[rows], M=rb[c + 1] - rb[c], gelu_grad_pre=ep["hid_pre"][rows],
-                            a_row_idx=pl.regroup, a_row_div=1, group_offsets=pl.offsets, tile_starts=pl.tile_starts)
-                ops.gemm_nt(dhp[rows], wt1[es], dx_recv[rows], M=rb[c + 1] - rb[c], c_row_idx=pl.regroup,
-                            group_offsets=pl.offsets, tile_starts=pl.tile_starts)
-            back.append(self._a2a_async(dx_send[sb[c]:sb[c + 1]], dx_recv[rows], pl.in_splits, pl.out_splits))
-        if n > 0:
-            rg = ep["rg"]
-            self._wgrad(dy_recv, ep["hid"], b + "mlp.experts.h4toh.weight", M=n, c_row_idx=rg,
-                        group_offsets=ep["offsets"], bias=b + "mlp.experts.h4toh.bias")
-            self._wgrad(dhp, ep["x_recv"], b + "mlp.experts.htoh4.weight", M=n, a_row_idx=rg, a_row_div=1,
-                        group_offsets=ep["offsets"], bias=b + "mlp.experts.htoh4.bias")
-        for w_ in back:
-            w_.wait()
-        ops.gather_rows(dx_send, r.pos, self.s_dxe)
-
-    def _a2a_equal(self, x, out):
-        """all-to-all with equal splits (the fixed-capacity exchange): no sizes, nothing for the host to read"""
-        import torch.distributed as dist
-        dist.all_to_all_single(out, x, group=self.ep_group)
-        return out
-
-    def _experts_fwd_ep_fixed(self, i, a, g):
-        """_experts_fwd_ep with ep_cap rows per (source, destination) pair: the send buffer is the padded [W * cap, D]
-        image gathered straight from h2 through pad_idx, rows arrive at source * cap + ..., the grouped GEMMs take the
-        device-resident regroup / offsets / tile prefix with M = the capacity bound (surplus workgroups retire on the
-        device-side tile prefix), and the outputs come home through unpad_idx."""
-        import torch.distributed as dist
-        b = f"blocks.{i}."
-        p, k = self.params, self.k
-        fx = self.ep_fx[i]
-        W, cap = self.ep_world, self.ep_cap
-        n = W * cap
-        r = ops.route_build(g["idx32"], self.E, want_counts64=True)
-        a["route"] = r
-        dist.all_to_all_single(fx["recv_counts"], r.counts64, group=self.ep_group)
-        plan = fx["plan"] = ops.ep_plan_fixed(r.counts64, fx["recv_counts"], W, self.E_loc, cap, r, self.ep_overflow,
-                                              bufs=fx["plan"])
-        ops.gather_rows(a["h2"], plan.pad_idx, fx["x_send"], div=k)
-        self._a2a_equal(fx["x_send"], fx["x_recv"])
-        ops.gemm_nt(fx["x_recv"], self.wc[b + "mlp.experts.htoh4"], fx["hid"], M=n, bias=p[b + "mlp.experts.htoh4.bias"],
-                    act=M3_ACT_GELU, pre_out=fx["hid_pre"], a_row_idx=plan.regroup, a_row_div=1,
-                    group_offsets=plan.offsets, tile_starts=plan.tile_starts)
-        ops.gemm_nt(fx["hid"], self.wc[b + "mlp.experts.h4toh"], fx["y_recv"], M=n, bias=p[b + "mlp.experts.h4toh.bias"],
-                    c_row_idx=plan.regroup, group_offsets=plan.offsets, tile_starts=plan.tile_starts)
-        self._a2a_equal(fx["y_recv"], fx["y_back"])
-        ops.gather_rows(fx["y_back"], plan.unpad_idx, a["y"])            # back to token-major [T*k, D]
-        a["ep"] = dict(fixed=True)
-
-    def _experts_bwd_ep_fixed(self, i, a):
-        b = f"blocks.{i}."
-        fx, fb = self.ep_fx[i], self.ep_fx_bwd
-        plan = fx["plan"]
-        n = self.ep_world * self.ep_cap
-        rg = plan.regroup
-        ops.gather_rows(self.s_dy, plan.pad_idx, fb["dy_send"])
-        self._a2a_equal(fb["dy_send"], fb["dy_recv"])
-        self._wgrad(fb["dy_recv"], fx["hid"], b + "mlp.experts.h4toh.weight", M=n, c_row_idx=rg,
-                    group_offsets=plan.offsets, bias=b + "mlp.experts.h4toh.bias")
-        ops.gemm_nt(fb["dy_recv"], self.wt[b + "mlp.experts.h4toh"], fb["dhp"], M=n, gelu_grad_pre=fx["hid_pre"],
-                    a_row_idx=rg, a_row_div=1, group_offsets=plan.offsets, tile_starts=plan.tile_starts)
-        self._wgrad(fb["dhp"], fx["x_recv"], b + "mlp.experts.htoh4.weight", M=n, a_row_idx=rg, a_row_div=1,
-                    group_offsets=plan.offsets, bias=b + "mlp.experts.htoh4.bias")
-        ops.gemm_nt(fb["dhp"], self.wt[b + "mlp.experts.htoh4"], fb["dx_recv"], M=n, c_row_idx=rg,
-                    group_offsets=plan.offsets, tile_starts=plan.tile_starts)
-        self._a2a_equal(fb["dx_recv"], fb["dx_back"])
-        ops.gather_rows(fb["dx_back"], plan.unpad_idx, self.s_dxe)
-
-    def ep_overflowed(self) -> bool:
-        """fixed-capacity exchange: did any (source, destination) pair of any layer since the last call route more rows
-        than the capacity?  ONE host read; clears the flag."""
-        if not self.ep_capacity:
-            return False
-        over = bool(int(self.ep_overflow.item()))
-        if over:
-            self.ep_overflow.zero_()
-        return over
-
-    def _experts_bwd_ep(self, i, a):
-        """mirror of _experts_fwd_ep: self.s_dy (token-major d y) -> expert grads (local experts only) and
-        self.s_dxe (token-major d of the routed input copies)."""
-        if a["ep"].get("fixed"):
-            return self._experts_bwd_ep_fixed(i, a)
-        if a["ep"].get("chunked"):
-            return self._experts_bwd_ep_chunked(i, a)
-        b = f"blocks.{i}."
-        k, D, r, ep = self.k, self.D, a["route"], a["ep"]
-        plan, n = ep["plan"], ep["n"]
-        dy_send = ops.gather_rows(self.s_dy, r.row_of_slot, self._e(self.R, D))
-        dy_recv = self._a2a(dy_send, plan.in_splits, plan.out_splits)
-        dx_recv = self._e(n, D)
-        if n > 0:
-            rg = ep["rg"]
-            self._wgrad(dy_recv, ep["hid"], b + "mlp.experts.h4toh.weight", M=n, c_row_idx=rg,
-                        group_offsets=ep["offsets"], bias=b + "mlp.experts.h4toh.bias")
-            dhp = self._e(n, self.Hm)
-            ops.gemm_nt(dy_recv, self.wt[b + "mlp.experts.h4toh"], dhp, M=n, gelu_grad_pre=ep["hid_pre"],
-                        a_row_idx=rg, a_row_div=1, group_offsets=ep["offsets"], tile_starts=ep["tile_starts"])
-            self._wgrad(dhp, ep["x_recv"], b + "mlp.experts.htoh4.weight", M=n, a_row_idx=rg, a_row_div=1,
-                        group_offsets=ep["offsets"], bias=b + "mlp.experts.htoh4.bias")
-            ops.gemm_nt(dhp, self.wt[b + "mlp.experts.htoh4"], dx_recv, M=n, c_row_idx=rg,
-                        group_offsets=ep["offsets"], tile_starts=ep["tile_starts"])
-        dx_send = self._a2a(dx_recv, plan.out_splits, plan.in_splits)
-        ops.gather_rows(dx_send, r.pos, self.s_dxe)
 
     def sync_grads(self, group=None, world: int = 1):
         """Data-parallel gradient sync (mean): everything when experts are replicated, only the non-expert
@@ -953,18 +675,8 @@ class BackboneEngine:
                     ops.combine_bwd(dx, a["y"], score, None, self.s_dscore)
                     if sm is not None:
                         self.s_dscore.mul_(a["sm_tok"])         # d score = scale * d(scale * score)
-                    dhp = self.s_dpre[: R * self.Hm].view(R, self.Hm)
-                    self._wgrad(self.s_dx_t, a["hid"], b + "mlp.experts.h4toh.weight", M=R, c_row_idx=r.row_of_slot,
-                                c_row_div=k, c_row_scale=score, group_offsets=r.offsets,
-                                bias=b + "mlp.experts.h4toh.bias", reads=("dx_t",))
-                    self._before_write("dpre")
-                    ops.gemm_nt(self.s_dx_t, self.wt[b + "mlp.experts.h4toh"], dhp, M=R, gelu_grad_pre=a["hid_pre"],
-                                a_row_idx=r.row_of_slot, a_row_div=k, row_scale=score, row_scale_idx=r.row_of_slot,
-                                group_offsets=r.offsets, tile_starts=r.tile_starts)
-                    self._wgrad(dhp, a["h2"], b + "mlp.experts.htoh4.weight", M=R, a_row_idx=r.row_of_slot,
-                                a_row_div=k, group_offsets=r.offsets, bias=b + "mlp.experts.htoh4.bias", reads=("dpre",))
-                    ops.gemm_nt(dhp, self.wt[b + "mlp.experts.htoh4"], self.s_dxe, M=R, c_row_idx=r.row_of_slot,
-                                group_offsets=r.offsets, tile_starts=r.tile_starts)
+                    self._ffn_bwd(i, self.s_dx_t, a["h2"], a["hid_pre"], a["hid"], self.s_dpre[: R * self.Hm].view(R, self.Hm),
+                                  self.s_dxe, R, r.row_of_slot, k, r.offsets, r.tile_starts, score=score)
                 # gate: d score from the combine, d importance / d load from the cv loss
                 cvw_dev = cv_weight if isinstance(cv_weight, torch.Tensor) else None
                 bal = cvw_dev is not None or cv_weight != 0.0

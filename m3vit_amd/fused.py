@@ -193,7 +193,7 @@ class FusedBackbone:
         self.names = list(named)
         params = {n: p.detach() for n, p in named.items()}
         # experts sharded over the ranks (world_size > 1, utils/common_config.py:179-185): the module holds this rank's
-        # moe_experts // world_size experts, the executor exchanges the routed rows (engine._experts_fwd_ep).  The exchange
+        # moe_experts // world_size experts, the executor exchanges the routed rows (engine_ep._experts_fwd_ep).  The exchange
         # reads its split sizes on the host, so these passes run eagerly (no hipGraph)
         self.moe_stats = bool(getattr(model, "moe_stats", False))
         self.stats_slot = None                   # the context of the most recent forward CALL (its records are that call's)
