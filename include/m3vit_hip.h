@@ -300,6 +300,27 @@ typedef struct {
   int32_t direct_beta, direct_beta_db;
 } m3_wgrad_args;
 int m3_wgrad_tn(const m3_wgrad_args *args, void *stream);
+/* How to cut a call up: fill m3_wgrad_shape, call m3_wgrad_plan (host code, no GPU work), copy splits / chunk_rows / units into
+ * m3_wgrad_args and give the call ws_elems floats of workspace (weight slabs first, then the bias slabs).  The plan follows the
+ * kernel m3_wgrad_tn takes for the shape under the current m3_wgrad_set_dma / m3_wgrad_set_big settings: the streaming kernel
+ * of m3_wgrad_skinny gets at least 64 rows per part and at most 256 parts, a tile kernel as many parts as fill its resident
+ * workgroups once (at least 512 rows each, dense calls in whole multiples of the 8 XCDs), and grouped calls of 2 .. 64 groups
+ * balanced units.  direct = 1 (only with direct_ok, when one part per group is enough): pass direct_dW / direct_db, no
+ * workspace, no reduction.  A caller may still set the three fields by itself - a call planned for one kernel runs correctly
+ * on another. */
+typedef struct {
+  int64_t M; int32_t N, K, G; int32_t dtype;
+  int32_t grouped;                 /* the call will pass group_offsets */
+  int32_t bias;                    /* the call wants the fused bias gradient (bias_ws / direct_db) */
+  int32_t splits;                  /* 0: the library's rule; >= 1: the caller's row parts */
+  int32_t direct_ok;               /* the caller can take direct mode (dW 16-byte aligned, adding into it is acceptable) */
+} m3_wgrad_shape;
+typedef struct {
+  int32_t splits, chunk_rows, units;   /* the fields of m3_wgrad_args of the same names */
+  int32_t direct;
+  int64_t ws_elems;                /* fp32 elements: units * N * (K + bias); 0 in direct mode */
+} m3_wgrad_plan_out;
+int m3_wgrad_plan(const m3_wgrad_shape *shape, m3_wgrad_plan_out *plan);
 /* Tuning knob, no reference counterpart: which weight-gradient launches take the LDS-DMA kernel (wgrad_dma_kernel,
  * csrc/wgrad.hip: four workgroups per CU, operands global -> LDS directly; fp16 / bf16 / fp32, power-of-two gather divisors, a
  * per-row factor with fp16 / fp32 only).  0 = none (the register-staged kernel everywhere), 2 = every launch the kernel can
@@ -313,13 +334,12 @@ int m3_wgrad_set_dma(int on);
  * shapes it takes; switch before sizing workspaces.  Same results up to fp32 summation order. */
 int m3_wgrad_set_big(int on);
 /* The output tile (n x k) m3_wgrad_tn uses for a shape: 256 x 256 where m3_wgrad_set_big's kernel takes it, else 128 x 128.
- * Callers that pick `splits` / `units` themselves size them (and the slab workspace splits * G * N * K) for
- * ceil(N / tn) * ceil(K / tk) tiles per group. */
+ * m3_wgrad_plan sizes `splits` / `units` for ceil(N / tn) * ceil(K / tk) tiles per group. */
 int m3_wgrad_tile(int N, int K, int dtype, int *tn, int *tk);
 /* 1 when m3_wgrad_tn runs a plain call of this shape (one group, no gathers / factor / bias / balanced units / direct mode) with
  * the streaming kernel for K = 16 / 32 - the router's weight, dW_gate = h^T d_logits (custom_moe_layer.py:213-217) - instead of
- * a 128 x 128 MFMA tile padded eightfold: the caller then sizes `splits` for a stream over dC (ops.default_wgrad_splits:
- * at least 64 rows per part, at most 256 parts).  Slab layout and reduction are unchanged.  M3_WGRAD_SKINNY=0 switches it off. */
+ * a 128 x 128 MFMA tile padded eightfold: m3_wgrad_plan then sizes `splits` for a stream over dC.  Slab layout and reduction
+ * are unchanged.  M3_WGRAD_SKINNY=0 switches it off. */
 int m3_wgrad_skinny(int N, int K, int G);
 /* balanced mode: dW[g] (+)= sum over group g's units of ws[u] (elems = N*K per group), unit order; optionally the
  * same for the bias slabs (bias_elems = N per group) */

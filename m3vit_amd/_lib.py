@@ -68,6 +68,15 @@ class WgradArgs(Structure):
     ]
 
 
+class WgradShape(Structure):
+    _fields_ = [("M", c_int64), ("N", c_int32), ("K", c_int32), ("G", c_int32), ("dtype", c_int32),
+                ("grouped", c_int32), ("bias", c_int32), ("splits", c_int32), ("direct_ok", c_int32)]
+
+
+class WgradPlan(Structure):
+    _fields_ = [("splits", c_int32), ("chunk_rows", c_int32), ("units", c_int32), ("direct", c_int32), ("ws_elems", c_int64)]
+
+
 class CastDesc(Structure):
     _fields_ = [("src", c_void_p), ("dst", c_void_p), ("dst_t", c_void_p), ("G", c_int32), ("rows", c_int32),
                 ("cols", c_int32), ("tile_start", c_int32)]
@@ -127,6 +136,7 @@ SIGNATURES = {
     "m3_gemm_nt": (c_int, [POINTER(GemmArgs), _V]),
     "m3_gemm_set_big": (c_int, [_I]),
     "m3_wgrad_tn": (c_int, [POINTER(WgradArgs), _V]),
+    "m3_wgrad_plan": (c_int, [POINTER(WgradShape), POINTER(WgradPlan)]),
     "m3_wgrad_tile": (c_int, [_I, _I, _I, POINTER(c_int), POINTER(c_int)]),
     "m3_wgrad_skinny": (c_int, [_I, _I, _I]),
     "m3_wgrad_set_dma": (c_int, [_I]),

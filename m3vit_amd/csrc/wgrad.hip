@@ -1264,6 +1264,19 @@ extern "C" int m3_wgrad_set_dma(int on) {
   g_wgrad_dma = on;
   return M3_OK;
 }
+// m3_wgrad_set_dma's rule for a launch of 128 x 128 tiles: 0 never, 2 always, 1 (default) where the LDS-DMA kernel measured
+// faster with operands streamed from HBM as inside the training step (tools/wgrad_ab_bench.py,
+// profiles/r05_wgrad_ab_streamed.txt): fp32 always (-12..-26 %); 16-bit when the launch has one part per group anyway - tiles x
+// groups fill the 1024 workgroup slots: direct accumulation, the ViT-Base experts, -35 % - or the weight is large (N K >= 1.5 M
+// elements: ViT-Base qkv / fc1 / fc2, -10..-24 %); at configs[1]'s 384-wide weights the register-staged kernel is level or
+// ahead (+-5 %) and keeps them.  m3_wgrad_plan counts workgroup slots by it; m3_wgrad_tn also asks whether the kernel can run
+// the call.
+static bool wgrad_dma_pays(int N, int K, int G, int dtype) {
+  if (g_wgrad_dma < 0) { const char *e = getenv("M3_WGRAD_DMA"); g_wgrad_dma = e ? atoi(e) : 1; }
+  if (g_wgrad_dma != 1) return g_wgrad_dma == 2;
+  const int64_t tiles = (int64_t)((N + WG_T - 1) / WG_T) * ((K + WG_T - 1) / WG_T) * G;
+  return dtype == M3_F32 || (int64_t)N * K >= 1500000 || tiles >= 1024;
+}
 
 static int g_wgrad_big = -1;
 extern "C" int m3_wgrad_set_big(int on) {
@@ -1276,9 +1289,8 @@ static bool wgrad_big_shape(int N, int K, int dtype) {
   return g_wgrad_big && dtype != M3_F32 && N % BG_T == 0 && K % BG_T == 0;
 }
 
-// the output tile (n x k) m3_wgrad_tn uses for a shape: callers size `splits` / `units` (and with them the slab
-// workspace) for ceil(N / tn) * ceil(K / tk) tiles per group: 256 x 256 for the 16-bit shapes the big-tile kernel takes,
-// else 128 x 128.
+// the output tile (n x k) m3_wgrad_tn uses for a shape: 256 x 256 for the 16-bit shapes the big-tile kernel takes, else
+// 128 x 128 (m3_wgrad_plan sizes `splits` / `units` for ceil(N / tn) * ceil(K / tk) tiles per group).
 extern "C" int m3_wgrad_tile(int N, int K, int dtype, int *tn, int *tk) {
   M3_REQUIRE(tn && tk, "m3_wgrad_tile: null output");
   *tn = *tk = wgrad_big_shape(N, K, dtype) ? BG_T : WG_T;
@@ -1299,6 +1311,64 @@ extern "C" int m3_wgrad_skinny(int N, int K, int G) {
   static int on = -1;
   if (on < 0) { const char *e = getenv("M3_WGRAD_SKINNY"); on = e ? (atoi(e) ? 1 : 0) : 1; }
   return on && G == 1 && (K == 16 || K == 32) && N % 2 == 0 && N >= 2;
+}
+
+// Row parts of a dense call in whole multiples of the 8 XCDs where that costs at most 1/8 of the parts: the tiles of a part
+// read the same rows, and the XCD remap hands every XCD an equal run of consecutive workgroups - with a multiple of 8 parts no
+// part straddles two XCDs (its rows then come into one L2, not two).
+static int64_t wgrad_whole_xcds(int64_t splits) {
+  const int64_t down = splits - splits % 8;
+  return splits >= 8 && 8 * down >= 7 * splits ? down : splits;
+}
+
+// The row parts the library cuts a call into by itself, for the kernel m3_wgrad_tn will take
+static int64_t wgrad_default_splits(int64_t M, int N, int K, int G, int dtype) {
+  if (m3_wgrad_skinny(N, K, G)) return std::max<int64_t>(1, std::min<int64_t>(256, M / 64));   // a stream over dC, 64+ rows per part (16 per wave)
+  const bool big = wgrad_big_shape(N, K, dtype);
+  const int t = big ? BG_T : WG_T;
+  const int64_t tiles = (int64_t)((N + t - 1) / t) * ((K + t - 1) / t) * G;
+  // at least 16 32-row steps per part, so that short contractions (few tokens) do not pay a 64 KiB slab write + reduce per
+  // handful of steps (measured on the 8-image configs; no effect at batch 128)
+  const int64_t steps = std::max<int64_t>(1, (M / G + 31) / 32), cap = std::max<int64_t>(1, steps / 16);
+  int64_t sp;
+  if (!big) {
+    // 128 x 128 tiles: fill the resident workgroup slots exactly once (the LDS-DMA kernel runs four workgroups per CU, the
+    // register-staged one two) - more parts only add slab traffic and a ragged second wave of workgroups.  fp32 is MFMA-bound
+    // (1/16 of the fp16 rate): its slots matter more than its slab bytes, so small weights (proj: 9 tiles) may be cut into as
+    // many parts as fill them; 16-bit stays at 32 (slab traffic; 44 / 56 measured level to +0.5 % at configs[1])
+    const int64_t slots = wgrad_dma_pays(N, K, G, dtype) ? 1024 : 512, most = dtype == M3_F32 ? 128 : 32;
+    sp = std::min(std::min(cap, most), tiles <= slots ? slots / tiles : 1);
+  } else {
+    // 256 x 256 tiles, one 8-wave workgroup per CU: fill the 256 slots once; with more tiles than slots (grouped experts) one
+    // part per group - the kernel then accumulates into dW itself (direct mode), no slabs
+    sp = tiles < 256 ? std::min(std::min<int64_t>(cap, 32), 256 / tiles) : 1;
+  }
+  sp = std::max<int64_t>(1, sp);
+  return G == 1 ? wgrad_whole_xcds(sp) : sp;
+}
+
+extern "C" int m3_wgrad_plan(const m3_wgrad_shape *s, m3_wgrad_plan_out *p) {
+  M3_REQUIRE(s && p, "m3_wgrad_plan: null argument");
+  M3_REQUIRE(dtype_ok(s->dtype), "m3_wgrad_plan: bad dtype");
+  M3_REQUIRE(s->N > 0 && s->K > 0 && s->M >= 0 && s->M < ((int64_t)1 << 31) && s->G >= 1 && s->splits >= 0, "m3_wgrad_plan: bad shape");
+  const int64_t M = s->M, G = s->G;
+  const int64_t sp = s->splits ? s->splits : wgrad_default_splits(M, s->N, s->K, s->G, s->dtype);
+  // direct mode: with ONE part per group every (group, tile) belongs to one workgroup, which adds its tile into dW itself.  The
+  // rule above says 1 exactly when the tiles alone fill the chip (the ViT-Base experts: 2304 tiles, 151 MB of gradient per layer)
+  const bool direct = s->direct_ok && sp == 1;
+  // grouped calls: work units of equal row counts dealt to the groups by their (device-resident) sizes, so that a hot expert
+  // gets more workgroups instead of longer ones; `splits` is the average number of units per group and the chunk sits 1/8
+  // above the mean part, so that groups near the mean keep `splits` units
+  int64_t chunk = 0, units = sp * G;
+  if (s->grouped && !direct && G > 1 && G <= 64 && M > 0) {
+    const int64_t part = (M * 9 + 8 * sp * G - 1) / (8 * sp * G);
+    chunk = std::max<int64_t>(64, (part + 63) / 64 * 64);
+    units = M / chunk + G;
+  }
+  M3_REQUIRE(units <= INT32_MAX, "m3_wgrad_plan: %lld slab slots", (long long)units);
+  p->splits = (int32_t)sp; p->chunk_rows = (int32_t)chunk; p->units = (int32_t)units; p->direct = direct;
+  p->ws_elems = direct ? 0 : units * s->N * (s->K + (s->bias ? 1 : 0));
+  return M3_OK;
 }
 
 extern "C" int m3_wgrad_tn(const m3_wgrad_args *a, void *stream) {
@@ -1418,17 +1488,10 @@ extern "C" int m3_wgrad_tn(const m3_wgrad_args *a, void *stream) {
   const size_t lds16 = 4 * WgLds<half_t>::ROWS * WgLds<half_t>::STRIDE, lds32 = 4 * WgLds<float>::ROWS * WgLds<float>::STRIDE;
   const bool sc = a->c_row_scale != nullptr;
   // LDS-DMA variant (wgrad_dma_kernel): whole 16-byte column chunks on both sides, power-of-two gather divisors, a per-row
-  // factor only with fp16 / fp32.  m3_wgrad_set_dma / M3_WGRAD_DMA: 0 never, 2 whenever the kernel can run the call, 1
-  // (default) where it measured faster with operands streamed from HBM as inside the training step
-  // (tools/wgrad_ab_bench.py, profiles/r05_wgrad_ab_streamed.txt): fp32 always (-12..-26 %); 16-bit when the launch has one
-  // part per group anyway - tiles x groups fill the 1024 workgroup slots: direct accumulation, the ViT-Base experts, -35 % -
-  // or the weight is large (N K >= 1.5 M elements: ViT-Base qkv / fc1 / fc2, -10..-24 %); at configs[1]'s 384-wide weights
-  // the register-staged kernel is level or ahead (+-5 %) and keeps them
-  if (g_wgrad_dma < 0) { const char *e = getenv("M3_WGRAD_DMA"); g_wgrad_dma = e ? atoi(e) : 1; }
+  // factor only with fp16 / fp32; taken where m3_wgrad_set_dma's rule (wgrad_dma_pays) asks for it
   const bool dma_can = (!sc || (gc && a->dtype != M3_BF16)) && a->N * es >= 16 && a->K * es >= 16 && d.a_row_sh >= 0 && d.c_row_sh >= 0 &&
                        (a->M + 1) * d.lddc_b < ((int64_t)1 << 32) && (a->M + 1) * d.lda_b < ((int64_t)1 << 32);       // 32-bit lane offsets
-  const bool dma_pays = es == 4 || (int64_t)a->N * a->K >= 1500000 || (int64_t)tiles_n * d.tiles_k * a->G >= 1024;
-  if (dma_can && (g_wgrad_dma == 2 || (g_wgrad_dma == 1 && dma_pays))) {
+  if (dma_can && wgrad_dma_pays(a->N, a->K, a->G, a->dtype)) {
     const size_t ldsd = 2 * 64 * WG_T * 2 + 256;       // 32 KiB + the step's per-row factors
 #define M3_WD(TT)                                                                                    \
     do {                                                                                             \

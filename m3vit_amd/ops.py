@@ -9,13 +9,14 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import gc
+import os
 from ctypes import byref, c_void_p
 from typing import Optional
 
 import torch
 
 from . import _lib
-from ._lib import M3_ACT_GELU, M3_ACT_NONE, M3_BF16, M3_F16, M3_F32, GemmArgs, WgradArgs, WgradReduceDesc, check, lib
+from ._lib import M3_ACT_GELU, M3_ACT_NONE, M3_BF16, M3_F16, M3_F32, GemmArgs, WgradArgs, WgradPlan, WgradReduceDesc, WgradShape, check, lib
 
 _DT = {torch.float32: M3_F32, torch.float16: M3_F16, torch.bfloat16: M3_BF16}      # bf16: every entry point
 
@@ -394,6 +395,19 @@ def gemm_set_big(mode: int):
     check(lib().m3_gemm_set_big(int(mode)), "m3_gemm_set_big")
 
 
+_WGRAD_DIRECT = os.environ.get("M3_WGRAD_DIRECT", "1") != "0"      # one part per group: the kernel accumulates into dW itself (no slabs)
+
+
+def _wgrad_reduce(d: WgradReduceDesc):
+    """launch the slab reduction a descriptor names"""
+    if d.chunk_rows:
+        check(lib().m3_wgrad_reduce_grouped(d.ws, d.group_offsets, d.G, d.chunk_rows, d.elems, d.dW, d.beta, d.bias_ws,
+                                            d.bias_elems, d.db, d.beta_db, _stream()), "m3_wgrad_reduce_grouped")
+    else:
+        check(lib().m3_wgrad_reduce(d.ws, d.splits, d.elems, d.dW, d.beta, d.bias_ws, d.bias_elems, d.db, d.beta_db,
+                                    _stream()), "m3_wgrad_reduce")
+
+
 class WgradQueue:
     """Weight-gradient calls of ONE stream whose slab reductions ride in front of the next call's launch
     (m3_wgrad_args.prev) instead of being launched by themselves: two slab workspaces used in turn, the reduction of the
@@ -415,14 +429,33 @@ class WgradQueue:
             return
         d, _keep = self.pending
         self.pending = None
-        if d.elems == 0:
-            return
-        if d.chunk_rows:
-            check(lib().m3_wgrad_reduce_grouped(d.ws, d.group_offsets, d.G, d.chunk_rows, d.elems, d.dW, d.beta, d.bias_ws,
-                                                d.bias_elems, d.db, d.beta_db, _stream()), "m3_wgrad_reduce_grouped")
-        else:
-            check(lib().m3_wgrad_reduce(d.ws, d.splits, d.elems, d.dW, d.beta, d.bias_ws, d.bias_elems, d.db, d.beta_db,
-                                        _stream()), "m3_wgrad_reduce")
+        if d.elems:
+            _wgrad_reduce(d)
+
+
+def wgrad_launch_plan(M, N, K, G, dtype, *, grouped, bias=True, splits=0, direct_ok=False) -> WgradPlan:
+    """How m3_wgrad_tn cuts this call up (m3_wgrad_plan in include/m3vit_hip.h): .splits / .chunk_rows / .units for
+    m3_wgrad_args, .direct, .ws_elems fp32 elements of slab workspace.  splits = 0: the library's rule."""
+    s = WgradShape(M, N, K, G, dt_code(dtype), bool(grouped), bool(bias), splits, bool(direct_ok))
+    p = WgradPlan()
+    check(lib().m3_wgrad_plan(byref(s), byref(p)), "m3_wgrad_plan")
+    return p
+
+
+def wgrad_plan(M, G, splits, grouped):
+    """(chunk_rows, slab slots) of a call cut into the caller's `splits` row parts (N, K and the dtype do not enter then)"""
+    p = wgrad_launch_plan(M, 1, 1, G, torch.float32, grouped=grouped, bias=False, splits=splits)
+    return p.chunk_rows, p.units
+
+
+def wgrad_ws_elems(M, N, K, G, grouped, bias=True, *, dtype):
+    """fp32 elements of workspace wgrad_tn needs for this shape with the default splits"""
+    return wgrad_launch_plan(M, N, K, G, dtype, grouped=grouped, bias=bias).ws_elems
+
+
+def default_wgrad_splits(M, N, K, G, dtype):
+    """row parts wgrad_tn cuts this shape into when the caller names none"""
+    return wgrad_launch_plan(M, N, K, G, dtype, grouped=G > 1).splits
 
 
 def wgrad_tn(dC, A, dW, *, M=None, beta=0, splits=None, ws=None, c_row_idx=None, a_row_idx=None, a_row_div=1,
@@ -437,27 +470,21 @@ def wgrad_tn(dC, A, dW, *, M=None, beta=0, splits=None, ws=None, c_row_idx=None,
     N, K = dW.shape[-2], dW.shape[-1]
     if M is None:
         M = c_row_idx.numel() if c_row_idx is not None else dC.shape[0]
+    bdb = beta if beta_db is None else beta_db
     if M == 0:                                   # nothing to contract over: no launch (an empty tensor has no address)
         if not beta:
             dW.zero_()
-        if db is not None and not (beta if beta_db is None else beta_db):
+        if db is not None and not bdb:
             db.zero_()
         return dW
-    if splits is None:
-        splits = default_wgrad_splits(M, N, K, G, dC.dtype)
-    # direct mode (include/m3vit_hip.h: m3_wgrad_args.direct_dW): with ONE part per group every (group, tile) belongs to one
-    # workgroup, which adds its tile into dW itself - no slabs, no reduction.  The default split rule says 1 exactly when the
-    # tiles alone fill the chip (the ViT-Base experts: 2304 tiles, 151 MB of gradient per layer)
-    direct = _WGRAD_DIRECT and splits == 1 and wgrad_tile(N, K, dC.dtype) in ((128, 128), (256, 256)) and dW.data_ptr() % 16 == 0
-    balanced = group_offsets is not None and not direct
-    chunk, units = wgrad_plan(M, G, splits, balanced)
-    balanced = chunk > 0
-    need = 0 if direct else units * N * K + (units * N if db is not None else 0)
+    # direct mode (include/m3vit_hip.h: m3_wgrad_args.direct_dW) where the plan has one part per group: no slabs, no reduction
+    p = wgrad_launch_plan(M, N, K, G, dC.dtype, grouped=group_offsets is not None, bias=db is not None, splits=splits or 0,
+                   direct_ok=_WGRAD_DIRECT and dW.data_ptr() % 16 == 0)
     if queue is not None:
         ws = queue.ws[queue.i]
-        assert ws.numel() >= need, "WgradQueue workspace too small for this shape"
-    elif ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 4), dtype=torch.float32, device=dW.device)
+        assert ws.numel() >= p.ws_elems, "WgradQueue workspace too small for this shape"
+    elif ws is None or ws.numel() < p.ws_elems:
+        ws = torch.empty(max(p.ws_elems, 4), dtype=torch.float32, device=dW.device)
     a = WgradArgs()
     a.dC = dC.data_ptr(); a.lddc = dC.stride(0)
     a.c_row_idx = c_row_idx.data_ptr() if c_row_idx is not None else None
@@ -471,106 +498,50 @@ def wgrad_tn(dC, A, dW, *, M=None, beta=0, splits=None, ws=None, c_row_idx=None,
     a.a_row_div = a_row_div
     a.M = M; a.N = N; a.K = K; a.G = G
     a.group_offsets = group_offsets.data_ptr() if group_offsets is not None else None
-    a.splits = splits
-    a.chunk_rows = chunk; a.units = units
+    a.splits = p.splits; a.chunk_rows = p.chunk_rows; a.units = p.units
     a.ws = ws.data_ptr()
     a.dtype = dt_code(dC.dtype)
-    bias_ws = ws[units * N * K:] if (db is not None and not direct) else None
-    a.bias_ws = bias_ws.data_ptr() if bias_ws is not None else None
-    bdb = beta if beta_db is None else beta_db
-    if direct:
-        if db is not None:
-            _req(db, torch.float32, "db")
+    if db is not None:
+        _req(db, torch.float32, "db")
+    prev = queue.pending if queue is not None else None
+    if p.direct:
         a.direct_dW = dW.data_ptr(); a.direct_beta = 1 if beta else 0
         a.direct_db = db.data_ptr() if db is not None else None
         a.direct_beta_db = 1 if bdb else 0
-        if queue is not None and queue.pending is not None:      # the previous call's reduction still rides in front
-            if queue.pending[0].dW == dW.data_ptr():              # ... unless it writes the tensor this launch read-add-writes
-                queue.flush()
-            else:
-                a.prev = ctypes.pointer(queue.pending[0])
-        check(lib().m3_wgrad_tn(byref(a), _stream()), "m3_wgrad_tn")
-        if queue is not None:
-            queue.pending = None                                  # (this call left nothing to reduce; its slab buffer was not used)
-        return dW
-    fuse = False
-    if db is not None:
-        _req(db, torch.float32, "db")
-        fuse = db.data_ptr() % 16 == 0 and bias_ws.data_ptr() % 16 == 0      # both slab reductions in one launch
-    if queue is not None:
-        assert db is None or fuse, "queued wgrad: db and the bias slabs must be 16-byte aligned"
-        prev = queue.pending
-        if prev is not None:
-            a.prev = ctypes.pointer(prev[0])
-        check(lib().m3_wgrad_tn(byref(a), _stream()), "m3_wgrad_tn")
+        if prev is not None and prev[0].dW == dW.data_ptr():       # the previous reduction writes the tensor this launch
+            queue.flush()                                          # read-add-writes: it cannot ride in front
+            prev = None
+    else:
+        # the reduction of this call's slabs; both slab kinds in one launch where db and the bias slabs are 16-byte aligned
+        bias_ws = ws[p.units * N * K:] if db is not None else None
+        a.bias_ws = bias_ws.data_ptr() if db is not None else None
+        fuse = db is not None and db.data_ptr() % 16 == 0 and bias_ws.data_ptr() % 16 == 0
+        assert db is None or fuse or queue is None, "queued wgrad: db and the bias slabs must be 16-byte aligned"
+        assert db is None or fuse or not p.chunk_rows, "balanced grouped wgrad: db and the bias slabs must be 16-byte aligned"
+        per = 1 if p.chunk_rows else G                              # balanced: elements per group, else of all groups
         d = WgradReduceDesc()
-        d.ws = ws.data_ptr(); d.splits = splits
-        d.elems = (N * K) if balanced else (G * N * K)
-        d.group_offsets = group_offsets.data_ptr() if balanced else None
-        d.G = G; d.chunk_rows = chunk if balanced else 0
+        d.ws = ws.data_ptr(); d.splits = p.splits; d.elems = per * N * K
+        d.group_offsets = a.group_offsets if p.chunk_rows else None
+        d.G = G; d.chunk_rows = p.chunk_rows
         d.dW = dW.data_ptr(); d.beta = beta
         d.bias_ws = bias_ws.data_ptr() if fuse else None
-        d.bias_elems = (N if balanced else G * N) if fuse else 0
+        d.bias_elems = per * N if fuse else 0
         d.db = db.data_ptr() if fuse else None
         d.beta_db = bdb
+    if prev is not None:                                           # the previous call's reduction rides in front
+        a.prev = ctypes.pointer(prev[0])
+    check(lib().m3_wgrad_tn(byref(a), _stream()), "m3_wgrad_tn")
+    if p.direct:                                                   # nothing to reduce (and the queue's slab buffer was not used)
+        if queue is not None:
+            queue.pending = None
+    elif queue is not None:
         queue.pending = (d, (ws, dW, db, group_offsets))
         queue.i ^= 1
-        return dW
-    check(lib().m3_wgrad_tn(byref(a), _stream()), "m3_wgrad_tn")
-    if balanced:
-        assert db is None or fuse, "balanced grouped wgrad: db and the bias slabs must be 16-byte aligned"
-        check(lib().m3_wgrad_reduce_grouped(_p(ws), _p(group_offsets), G, chunk, N * K, _p(dW), beta,
-                                            _p(bias_ws) if fuse else None, N, _p(db) if fuse else None, bdb, _stream()),
-              "m3_wgrad_reduce_grouped")
-        return dW
-    check(lib().m3_wgrad_reduce(_p(ws), splits, G * N * K, _p(dW), beta, _p(bias_ws) if fuse else None, G * N,
-                                _p(db) if fuse else None, bdb, _stream()), "m3_wgrad_reduce")
-    if db is not None and not fuse:
-        check(lib().m3_wgrad_bias_reduce(_p(bias_ws), splits, G * N, _p(db), bdb, _stream()), "m3_wgrad_bias_reduce")
+    else:
+        _wgrad_reduce(d)
+        if db is not None and not fuse:
+            check(lib().m3_wgrad_bias_reduce(_p(bias_ws), p.splits, G * N, _p(db), bdb, _stream()), "m3_wgrad_bias_reduce")
     return dW
-
-
-def wgrad_plan(M, G, splits, grouped):
-    """(chunk_rows, slab slots) of a weight-gradient call.  Grouped calls: work units of equal row counts dealt to the
-    groups by their (device-resident) sizes, so that a hot expert gets more workgroups instead of longer ones; `splits`
-    is the average number of units per group and the chunk sits 1/8 above the mean part, so that groups near the mean keep
-    `splits` units.  chunk 0: every group in `splits` equal parts."""
-    if grouped and 1 < G <= 64 and M > 0:
-        chunk = max(64, (-(-M * 9 // (8 * splits * G)) + 63) // 64 * 64)
-        return chunk, M // chunk + G
-    return 0, splits * G
-
-
-def wgrad_ws_elems(M, N, K, G, grouped, bias=True, dtype=None):
-    """fp32 elements of workspace wgrad_tn needs for this shape with the default splits"""
-    _, units = wgrad_plan(M, G, default_wgrad_splits(M, N, K, G, dtype), grouped)
-    return units * N * (K + (1 if bias else 0))
-
-
-_WGRAD_MIN_STEPS = 16      # 32-row steps per split at least (measured on the 8-image configs; no effect at batch 128)
-import os as _os
-_WGRAD_DIRECT = _os.environ.get("M3_WGRAD_DIRECT", "1") != "0"      # splits == 1: the kernel accumulates into dW itself (no slabs)
-# workgroup slots a weight-gradient launch is split to fill: the LDS-DMA kernel runs four workgroups per CU, the
-# register-staged one two; which kernel takes a launch is m3_wgrad_tn's rule (include/m3vit_hip.h: m3_wgrad_set_dma),
-# mirrored in _wgrad_uses_dma (measured with streamed operands: tools/wgrad_ab_bench.py, profiles/r05_wgrad_ab_streamed.txt)
-_WGRAD_MOST16 = int(_os.environ.get("M3_WGRAD_MOST16", "32"))       # most row parts of a 16-bit weight gradient (A/B knob; 44 / 56 measured level to +0.5 % at configs[1])
-_WGRAD_XCD_ALIGN = _os.environ.get("M3_WGRAD_XCD_ALIGN", "1") != "0"
-_WGRAD_SLOTS = int(_os.environ.get("M3_WGRAD_SLOTS", "0"))         # 0: by kernel (1024 / 512)
-_WGRAD_DMA = int(_os.environ.get("M3_WGRAD_DMA", "1"))              # 0 never, 1 where it pays (default), 2 wherever it can run
-
-
-def _wgrad_uses_dma(N, K, G, dtype, tiles_total):
-    if _WGRAD_DMA == 0:
-        return False
-    if _WGRAD_DMA == 2 or dtype == torch.float32:
-        return True
-    return N * K >= 1500000 or tiles_total >= 1024
-
-
-def _wgrad_slots(dtype, N=0, K=0, G=1, tiles_total=0):
-    if _WGRAD_SLOTS:
-        return _WGRAD_SLOTS
-    return 1024 if _wgrad_uses_dma(N, K, G, dtype, tiles_total) else 512
 
 
 def wgrad_set_big(on: int):
@@ -583,9 +554,7 @@ def wgrad_set_dma(on: int):
     """LDS-DMA weight-gradient kernel: 0 never / 1 where it pays (default) / 2 wherever it can run / -1 from M3_WGRAD_DMA
     (include/m3vit_hip.h: m3_wgrad_set_dma);
     switch before sizing workspaces (the default row splits follow the kernel's workgroups per CU)"""
-    global _WGRAD_DMA
     check(lib().m3_wgrad_set_dma(int(on)), "m3_wgrad_set_dma")
-    _WGRAD_DMA = int(_os.environ.get("M3_WGRAD_DMA", "1")) if int(on) < 0 else int(on)
 
 
 def wgrad_tile(N, K, dtype=None):
@@ -600,40 +569,6 @@ def wgrad_tile(N, K, dtype=None):
 def wgrad_skinny(N, K, G=1) -> bool:
     """m3_wgrad_tn takes plain calls of this shape (K = 16 / 32, one group) with the streaming kernel (m3_wgrad_skinny)"""
     return bool(lib().m3_wgrad_skinny(int(N), int(K), int(G)))
-
-
-def _xcd_aligned(splits):
-    """Row parts of a dense call in whole multiples of the 8 XCDs where that costs at most 1/8 of the parts: the tiles of a part
-    read the same rows, and the XCD remap hands every XCD an equal run of consecutive workgroups - with a multiple of 8 parts no
-    part straddles two XCDs (its rows then come into one L2, not two).  M3_WGRAD_XCD_ALIGN=0 switches it off."""
-    if not _WGRAD_XCD_ALIGN or splits < 8:
-        return splits
-    down = splits - splits % 8
-    return down if 8 * down >= 7 * splits else splits
-
-
-def default_wgrad_splits(M, N, K, G, dtype=None):
-    """Row splits of the TN GEMM.  128 x 128 tiles: fill the 512 resident workgroup slots (2 per CU) exactly once - more
-    splits only add slab traffic and a ragged second wave of workgroups - but keep at least _WGRAD_MIN_STEPS 32-row
-    steps per split, so that short contractions (few tokens) do not pay a 64 KiB slab write + reduce per handful of
-    steps."""
-    if wgrad_skinny(N, K, G):                       # the router's weight: a stream over dC, 64+ rows per part (16 per wave)
-        return int(max(1, min(256, M // 64)))
-    tn, tk = wgrad_tile(N, K, dtype)
-    tiles = ((N + tn - 1) // tn) * ((K + tk - 1) // tk) * G
-    steps = max(1, (M // max(G, 1) + 31) // 32)
-    cap = max(1, steps // _WGRAD_MIN_STEPS)
-    if (tn, tk) == (128, 128):
-        nslots = _wgrad_slots(dtype, N, K, G, tiles)
-        # fp32 is MFMA-bound (1/16 of the fp16 rate): its workgroup slots matter more than its slab bytes, so small weights
-        # (proj: 9 tiles) may be cut into as many parts as fill them; 16-bit stays at 32 (slab traffic)
-        most = 128 if dtype == torch.float32 else _WGRAD_MOST16
-        sp = int(max(1, min(cap, most, nslots // tiles if tiles <= nslots else 1)))
-        return _xcd_aligned(sp) if G == 1 else sp
-    # 256 x 256 tiles, one 8-wave workgroup per CU: fill the 256 slots once; with more tiles than slots (grouped experts) one
-    # part per group - the kernel then accumulates into dW itself (direct mode), no slabs
-    sp = int(max(1, min(cap, 32, 256 // tiles))) if tiles < 256 else 1
-    return _xcd_aligned(sp) if G == 1 else sp
 
 
 def colsum(dC, db, *, M=None, beta=0, c_row_idx=None, group_offsets=None, ws=None):

@@ -78,9 +78,9 @@ def run(ops, dtype, M, N, K, *, G=1, counts=None, splits=None, beta=0, want_db=T
     dC = rnd(rows_c, N, dtype=dtype, seed=1) if dC is None else dC
     A = rnd(rows_a, K, dtype=dtype, seed=2) if A is None else A
     grouped = off is not None
-    sp = ops.default_wgrad_splits(M, N, K, G, dtype) if splits is None else splits
-    _, units = ops.wgrad_plan(M, G, sp, grouped and G <= 64)
-    need = units * N * (K + (1 if want_db else 0))
+    p = ops.wgrad_launch_plan(M, N, K, G, dtype, grouped=grouped, bias=want_db, splits=splits or 0)
+    sp, need = p.splits, p.ws_elems                               # (slabs: this workspace is sized as for a call without direct mode)
+    assert need == p.units * N * (K + (1 if want_db else 0))
     if splits is None:
         assert need == ops.wgrad_ws_elems(M, N, K, G, grouped, bias=want_db, dtype=dtype)
     ws, wcheck = kc.guarded_ws(need)

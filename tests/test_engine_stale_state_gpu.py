@@ -429,7 +429,7 @@ def test_launch_plan_variants(variant, dtype, monkeypatch):
 def test_poison_stays_where_nothing_should_write(direct, monkeypatch):
     """the slab workspaces of the weight gradients past the largest slab need of any call of the step keep the sentinel
     (include/m3vit_hip.h: slabs are units * N * K (+ units * N) floats from the start of ws; a direct-mode call writes none).
-    The need of each call is ops.wgrad_plan's, recorded by a wrapper around ops.wgrad_tn - not taken from the buffers."""
+    The need of each call is ops.wgrad_launch_plan's, recorded by a wrapper around ops.wgrad_tn - not taken from the buffers."""
     _need_gpu()
     from m3vit_amd import engine as eng_mod
     from m3vit_amd import ops
@@ -442,12 +442,10 @@ def test_poison_stays_where_nothing_should_write(direct, monkeypatch):
         G = 1 if dW.dim() == 2 else dW.shape[0]
         N, K = dW.shape[-2], dW.shape[-1]
         m = M if M is not None else (c_row_idx.numel() if c_row_idx is not None else dC.shape[0])
-        sp = ops.default_wgrad_splits(m, N, K, G, dC.dtype) if splits is None else splits
-        is_direct = (ops._WGRAD_DIRECT and sp == 1 and ops.wgrad_tile(N, K, dC.dtype) in ((128, 128), (256, 256))
-                     and dW.data_ptr() % 16 == 0)
-        if not is_direct:
-            _, units = ops.wgrad_plan(m, G, sp, group_offsets is not None)
-            need[0] = max(need[0], units * N * K + (units * N if db is not None else 0))
+        p = ops.wgrad_launch_plan(m, N, K, G, dC.dtype, grouped=group_offsets is not None, bias=db is not None, splits=splits or 0,
+                           direct_ok=ops._WGRAD_DIRECT and dW.data_ptr() % 16 == 0)
+        assert p.ws_elems == (0 if p.direct else p.units * N * K + (p.units * N if db is not None else 0))
+        need[0] = max(need[0], p.ws_elems)
         return real(dC, A, dW, M=M, splits=splits, group_offsets=group_offsets, db=db, c_row_idx=c_row_idx, **kw)
 
     monkeypatch.setattr(eng_mod.ops, "wgrad_tn", spy)

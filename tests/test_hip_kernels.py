@@ -276,8 +276,8 @@ def test_wgrad_queue_rides_the_reduction_on_the_next_launch(ops):
         torch.cuda.synchronize()
         return outs
     want = run(None)
-    need = max(ops.wgrad_ws_elems(c["kw"].get("M", c["dC"].shape[0]), c["shape"][-2], c["shape"][-1],
-                                  c["shape"][0] if len(c["shape"]) == 3 else 1, grouped="group_offsets" in c["kw"], dtype=dt)
+    need = max(ops.wgrad_launch_plan(c["kw"].get("M", c["dC"].shape[0]), c["shape"][-2], c["shape"][-1],
+                              c["shape"][0] if len(c["shape"]) == 3 else 1, dt, grouped="group_offsets" in c["kw"]).ws_elems
                for c in calls)
     got = run(ops.WgradQueue(need, dev()))
     for i, ((w0, b0), (w1, b1)) in enumerate(zip(want, got)):
