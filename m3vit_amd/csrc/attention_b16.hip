@@ -1,27 +1,31 @@
-// Attention forward / backward for SHORT sequences (N <= 256 tokens, fp16, head dim 32 or 64): the case of
-// the 224x224 configurations (N = 197; ViT-S heads of 32, ViT-B heads of 64), where one (image, head) pair is
-// only 197 x 64 / 128 bytes per operand.  Same maths and operand plan as attention.hip (Attention.forward,
-// models/moe/ckpt/vision_transformer_moe.py:299-313), but everything a workgroup needs is staged
-// ONCE: K / V (forward) or Q / dO / K (backward) live in LDS for the whole kernel, so the loops over
-// the query tiles run without global-memory latency and with at most one barrier per step.
+// Attention forward / backward for the 16-bit dtypes (fp16 and bf16, head dim 32 or 64; every kernel is templated on the
+// element type).  Same maths as the exact-fp32 kernels of attention_f32.hip (Attention.forward,
+// models/moe/ckpt/vision_transformer_moe.py:299-313), in two families that attention.hip picks between by N:
 //
-// LDS images are row-major rows of dh halves (64 or 128 bytes), XOR-swizzled at 16-byte granularity
-// (64-byte rows: chunk ^= (row >> 1) & 3; 128-byte rows: chunk ^= row & 7): conflict-free both for
-// ds_read_b128 row fragments (contraction along the row) and for ds_read_b64_tr_b16 transposed fragments
-// (contraction along the rows), so no transposed copies are kept.
+// LDS-RESIDENT kernels, N <= ATTN_KEYS (256) tokens: the case of the 224x224 configurations (N = 197; ViT-S heads of 32,
+// ViT-B heads of 64), where one (image, head) pair is only 197 x 64 / 128 bytes per operand.  Everything a workgroup
+// needs is staged ONCE: K / V (forward) or Q / dO / K (backward) live in LDS for the whole kernel, so the loops over
+// the query tiles run without global-memory latency and with at most one barrier per step.
 //   fwd : wave owns query tiles {w, w+4, ..}: S^T[key][q] = K Q^T for ALL keys (<= 16 tiles in
 //         registers), plain softmax (no online rescaling), O^T[d][q] = V^T P^T.
 //   bwd : wave owns key tiles {w, w+NW, ..} (NW = 4 waves for dh 32, 8 for dh 64; dK^T, dV^T in registers),
 //         sweeps 32-row query steps:
 //         S = Q K^T, dP = dO V^T, P = exp(S - lse), dS = P (dP - delta);  dV^T += dO^T P,
 //         dK^T += Q^T dS;  dS^T goes to a double-buffered LDS image for dQ^T = K^T dS^T.
-#include "common.h"
+//
+// STREAMED kernels, longer sequences (second half of the file, described there): K / V tiles (forward) or Q / dO rows
+// (backward, one workgroup per ATTN_KEYS-key block, dQ left in the fp32 slabs of attention_dev.h) pass through an LDS ring.
+//
+// LDS images are row-major rows of dh 16-bit elements (64 or 128 bytes), XOR-swizzled at 16-byte granularity
+// (64-byte rows: chunk ^= (row >> 1) & 3; 128-byte rows: chunk ^= row & 7): conflict-free both for
+// ds_read_b128 row fragments (contraction along the row) and for ds_read_b64_tr_b16 transposed fragments
+// (contraction along the rows), so no transposed copies are kept.
+#include "attention_dev.h"
 #include <type_traits>
 
 namespace m3 {
 
 constexpr int AR_THREADS = 256;
-constexpr int AR_MAXN = 256;
 constexpr float AR_LOG2E = 1.4426950408889634f;
 
 typedef __fp16 ar_fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
@@ -170,7 +174,7 @@ __global__ __launch_bounds__(AR_THREADS, DH == 32 ? 4 : 2) void attention_fwd_re
 }
 
 // Diagnostic build only (-DM3_ATTN_STAMPS, tools/attn_stamps.py): lane 0 of wave 0 of every workgroup of the
-// short-sequence backward records s_memtime at its phase boundaries; no stamp executes in the shipped kernel.
+// LDS-resident backward records s_memtime at its phase boundaries; no stamp executes in the shipped kernel.
 #ifdef M3_ATTN_STAMPS
 constexpr int ASTAMP_WGS = 2048, ASTAMP_N = 40;
 __device__ unsigned long long g_attn_stamps[ASTAMP_WGS][ASTAMP_N];
@@ -198,7 +202,7 @@ __global__ __launch_bounds__(DH == 32 ? 256 : 512, DH == 32 ? 2 : 1) void attent
   constexpr int NW = DH == 32 ? 4 : 8, NT = NW * 64;
   constexpr int NKEY = KTE * NW * 16, NKC = NKEY / 32;      // keys covered by the wave tiles; 32-key chunks of the dQ contraction
   static_assert(2 * NDT == NW, "one dQ piece per wave");
-  static_assert(NKEY <= AR_MAXN, "at most 256 keys");
+  static_assert(NKEY <= ATTN_KEYS, "at most 256 keys");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int NP = (N + 31) & ~31;                       // query rows, padded to the 32-row steps (NP <= NKEY)
   char *sQ = smem, *sdO = sQ + NP * RBY, *sK = sdO + NP * RBY;        // sK: [NKEY keys][RBY], rows >= N zero
@@ -525,12 +529,10 @@ static int launch_attention_fwd_stream_t(const void *qkv, int B, int N, int head
                                 hipStream_t s) {
   const dim3 grid((N + 63) / 64, B * heads);
   const size_t lds = (size_t)4 * 64 * dh * 2;
-  if (dh == 32)
-    hipLaunchKernelGGL((attention_fwd_stream_kernel<T, 32>), grid, dim3(AR_THREADS), lds, s, (const T *)qkv, N, heads,
-                       (T *)o, lse, scale);
-  else
-    hipLaunchKernelGGL((attention_fwd_stream_kernel<T, 64>), grid, dim3(AR_THREADS), lds, s, (const T *)qkv, N, heads,
-                       (T *)o, lse, scale);
+#define M3_AFS_GO(DH_) hipLaunchKernelGGL((attention_fwd_stream_kernel<T, DH_>), grid, dim3(AR_THREADS), lds, s, (const T *)qkv, N, heads, \
+                                          (T *)o, lse, scale)
+  if (dh == 32) M3_AFS_GO(32); else M3_AFS_GO(64);
+#undef M3_AFS_GO
   return check_launch("m3_attention_fwd");
 }
 
@@ -562,22 +564,22 @@ __global__ __launch_bounds__(DH == 32 ? 256 : 512, DH == 32 ? 2 : 1) void attent
     const T *__restrict__ qkv, const T *__restrict__ d_o, const float *__restrict__ lse,
     const float *__restrict__ delta, int N, int heads, T *__restrict__ dqkv, float *__restrict__ dq_ws, float scale) {
   constexpr int RBY = DH * 2, CPR = RBY / 16, NCH = DH / 32, NDT = DH / 16;
-  constexpr int NW = DH == 32 ? 4 : 8, NT = NW * 64, KTW = 16 / NW, KB = 256;
+  constexpr int NW = DH == 32 ? 4 : 8, NT = NW * 64, KTW = 16 / NW;
   static_assert(2 * NDT == NW && 32 * CPR * 2 == NT, "one dQ piece and one staged chunk per thread");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char *sK = smem;                                     // [256 keys][RBY]
-  char *sQ = sK + KB * RBY;                            // [2][32 rows][RBY]
+  char *sQ = sK + ATTN_KEYS * RBY;                            // [2][32 rows][RBY]
   char *sdO = sQ + 2 * 32 * RBY;
   char *sdS = sdO + 2 * 32 * RBY;                      // [2][256 keys][64 B]
-  float *sLse = (float *)(sdS + 2 * KB * 64);          // [2][32]: lse * log2(e)
+  float *sLse = (float *)(sdS + 2 * ATTN_KEYS * 64);          // [2][32]: lse * log2(e)
   float *sDelta = sLse + 64;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lg = lane >> 4;
-  const int nkb = (N + KB - 1) / KB;
+  const int nkb = (N + ATTN_KEYS - 1) / ATTN_KEYS;
   const int wid = xcd_remap(blockIdx.x, gridDim.x);
   const int bh = wid / nkb, kbi = wid - bh * nkb, b = bh / heads, h = bh - b * heads;
-  const int kb0 = kbi * KB;
+  const int kb0 = kbi * ATTN_KEYS;
   const int C = heads * DH;
   const int64_t ld = 3 * (int64_t)C;
   const T *qbase = qkv + (int64_t)b * N * ld + h * DH;
@@ -587,18 +589,18 @@ __global__ __launch_bounds__(DH == 32 ? 256 : 512, DH == 32 ? 2 : 1) void attent
   const float *lbase = lse + ((int64_t)b * heads + h) * N;
   const float *dbase = delta + (int64_t)b * N * heads + h;             // [token][head]
   float *dqw = dq_ws + ((int64_t)kbi * (gridDim.x / nkb) + bh) * N * DH;
-  const int nkeys = (N - kb0 < KB) ? N - kb0 : KB;
+  const int nkeys = (N - kb0 < ATTN_KEYS) ? N - kb0 : ATTN_KEYS;
   const int nkt = (nkeys + 15) >> 4;                  // valid key tiles of this block
   const int nkc = (nkeys + 31) >> 5;                  // 32-key chunks that matter for dQ
 
   // ---- K image of the key block, zero the dS^T images
-  for (int q = tid; q < KB * CPR; q += NT) {
+  for (int q = tid; q < ATTN_KEYS * CPR; q += NT) {
     const int row = q / CPR, c = q % CPR;
     u32x4 kv = u32x4{0u, 0u, 0u, 0u};
     if (row < nkeys) kv = *(const u32x4 *)((const char *)(kbase + (int64_t)(kb0 + row) * ld) + c * 16);
     *(u32x4 *)(sK + swo<DH>(row, c * 16)) = kv;
   }
-  for (int q = tid; q < 2 * KB * 4; q += NT) *(u32x4 *)(sdS + q * 16) = u32x4{0u, 0u, 0u, 0u};
+  for (int q = tid; q < 2 * ATTN_KEYS * 4; q += NT) *(u32x4 *)(sdS + q * 16) = u32x4{0u, 0u, 0u, 0u};
   typename Mma<T>::frag kf[KTW][NCH], vf[KTW][NCH];
 #pragma unroll
   for (int kt = 0; kt < KTW; ++kt) {
@@ -655,7 +657,7 @@ __global__ __launch_bounds__(DH == 32 ? 256 : 512, DH == 32 ? 2 : 1) void attent
   for (int st = 0; st < nsteps; ++st) {
     const int qs = st * 32, buf = st & 1;
     const char *cQ = sQ + buf * 32 * RBY, *cdO = sdO + buf * 32 * RBY;
-    char *dsb = sdS + buf * KB * 64;
+    char *dsb = sdS + buf * ATTN_KEYS * 64;
     u32x4 nv; float nl2, ndl;
     const bool more = st + 1 < nsteps;
     if (more) fetch(qs + 32, nv, nl2, ndl);            // rows of the next step: in flight under this step's MFMAs
@@ -732,23 +734,23 @@ __global__ __launch_bounds__(DH == 32 ? 256 : 512, DH == 32 ? 2 : 1) void attent
     {
       const int qt = wave / NDT, dt = wave - qt * NDT;
       // all fragment reads first (clamped chunk index: always inside the images), then the dependent MFMA chain
-      typename Mma<T>::frag ka[AR_MAXN / 32], da[AR_MAXN / 32];
+      typename Mma<T>::frag ka[ATTN_KEYS / 32], da[ATTN_KEYS / 32];
 #pragma unroll
-      for (int c = 0; c < AR_MAXN / 32; ++c) {
+      for (int c = 0; c < ATTN_KEYS / 32; ++c) {
         const int cc = (FULL || c < nkc) ? c : nkc - 1;
         ka[c] = tr_frag<T, DH>(sK, cc * 32, dt * 16, li, lg);
         da[c] = tr_frag<T, 32>(dsb, cc * 32, qt * 16, li, lg);
       }
       f32x4 acc = zero4;
 #pragma unroll
-      for (int c = 0; c < AR_MAXN / 32; ++c)
+      for (int c = 0; c < ATTN_KEYS / 32; ++c)
         if (FULL || c < nkc) acc = Mma<T>::mma(ka[c], da[c], acc);
       const int qr = qs + qt * 16 + li;
       if (qr < N) *(f32x4 *)(dqw + (int64_t)qr * DH + dt * 16 + 4 * lg) = acc * scale;
     }
   }
   };
-  if (nkeys == KB) run(std::true_type{}); else run(std::false_type{});
+  if (nkeys == ATTN_KEYS) run(std::true_type{}); else run(std::false_type{});
 
   // ---- dK, dV rows of this wave's keys
 #pragma unroll
@@ -764,14 +766,14 @@ __global__ __launch_bounds__(DH == 32 ? 256 : 512, DH == 32 ? 2 : 1) void attent
   }
 }
 
-size_t attn_stream_bwd_lds(int dh) { return (size_t)256 * dh * 2 + 4 * 32 * dh * 2 + 2 * 256 * 64 + 128 * sizeof(float); }
+static size_t attn_stream_bwd_lds(int dh) { return (size_t)ATTN_KEYS * dh * 2 + 4 * 32 * dh * 2 + 2 * ATTN_KEYS * 64 + 128 * sizeof(float); }
 
-// dq_ws: [nkb][B*heads][N][dh] slabs followed by delta [B*N*heads]
+// dq_ws: the dQ slabs followed by delta (attn_bwd_ws)
 template <typename T>
 static int launch_attention_bwd_stream_t(const void *qkv, const void *o, const void *d_o, const float *lse, int B, int N, int heads,
                                 int dh, void *dqkv, float *dq_ws, float scale, hipStream_t s) {
-  const int nkb = (N + 255) / 256;
-  float *delta = dq_ws + (int64_t)nkb * B * heads * N * dh;
+  const int nkb = attn_key_blocks(N);
+  float *delta = dq_ws + attn_bwd_ws(B, N, heads, dh).delta_off;
   const int64_t rows = (int64_t)B * N;
   const unsigned dblocks = (unsigned)((rows * heads + 63) / 64);
   static bool attr_set = false;
@@ -782,25 +784,20 @@ static int launch_attention_bwd_stream_t(const void *qkv, const void *o, const v
                               (int)attn_stream_bwd_lds(64));
     attr_set = true;
   }
-  if (dh == 32) {
-    hipLaunchKernelGGL((attention_delta_kernel<T, 32>), dim3(dblocks), dim3(64), 0, s, (const T *)o, (const T *)d_o, rows,
-                       heads, delta);
-    hipLaunchKernelGGL((attention_bwd_stream_kernel<T, 32>), dim3(B * heads * nkb), dim3(256), attn_stream_bwd_lds(32), s,
-                       (const T *)qkv, (const T *)d_o, lse, delta, N, heads, (T *)dqkv, dq_ws, scale);
-  } else {
-    hipLaunchKernelGGL((attention_delta_kernel<T, 64>), dim3(dblocks), dim3(64), 0, s, (const T *)o, (const T *)d_o, rows,
-                       heads, delta);
-    hipLaunchKernelGGL((attention_bwd_stream_kernel<T, 64>), dim3(B * heads * nkb), dim3(512), attn_stream_bwd_lds(64), s,
-                       (const T *)qkv, (const T *)d_o, lse, delta, N, heads, (T *)dqkv, dq_ws, scale);
-  }
+#define M3_ABS_GO(DH_, NT_)                                                                                                   \
+  hipLaunchKernelGGL((attention_delta_kernel<T, DH_>), dim3(dblocks), dim3(64), 0, s, (const T *)o, (const T *)d_o, rows, heads, delta); \
+  hipLaunchKernelGGL((attention_bwd_stream_kernel<T, DH_>), dim3(B * heads * nkb), dim3(NT_), attn_stream_bwd_lds(DH_), s,    \
+                     (const T *)qkv, (const T *)d_o, lse, delta, N, heads, (T *)dqkv, dq_ws, scale)
+  if (dh == 32) { M3_ABS_GO(32, 256); } else { M3_ABS_GO(64, 512); }
+#undef M3_ABS_GO
   return check_launch("m3_attention_bwd");
 }
 
 static inline int attn_res_fwd_nkt(int N) { return ((N + 15) / 16 + 3) / 4 * 4; }      // key tiles rounded up to 4, 8, 12, 16
-size_t attn_res_fwd_lds(int N, int dh) { return (size_t)2 * attn_res_fwd_nkt(N) * 16 * dh * 2; }
-// tiles per wave of the short-sequence backward for N keys: ceil(key tiles / waves); LDS of that instance
+static size_t attn_res_fwd_lds(int N, int dh) { return (size_t)2 * attn_res_fwd_nkt(N) * 16 * dh * 2; }
+// tiles per wave of the LDS-resident backward for N keys: ceil(key tiles / waves); LDS of that instance
 static inline int attn_res_bwd_kte(int N, int dh) { const int nw = dh == 32 ? 4 : 8; return ((N + 15) / 16 + nw - 1) / nw; }
-size_t attn_res_bwd_lds(int N, int dh) {
+static size_t attn_res_bwd_lds(int N, int dh) {
   const size_t np = (N + 31) & ~31;
   const size_t nkey = (size_t)attn_res_bwd_kte(N, dh) * (dh == 32 ? 4 : 8) * 16;
   return 2 * np * dh * 2 + nkey * dh * 2 + 2 * nkey * 64 + 2 * np * sizeof(float);
@@ -846,22 +843,21 @@ static int launch_attention_bwd_res_t(const void *qkv, const void *o, const void
   return check_launch("m3_attention_bwd");
 }
 
-// fp16 / bf16 front doors (attention.hip picks these kernels for every 16-bit dtype)
+// front doors: attention.hip sends every 16-bit dtype here
+#define M3_B16(fn, ...) (dtype == M3_BF16 ? fn<bf16_t>(__VA_ARGS__) : fn<half_t>(__VA_ARGS__))
 int launch_attention_fwd_stream(int dtype, const void *qkv, int B, int N, int heads, int dh, void *o, float *lse, float scale, hipStream_t s) {
-  return dtype == M3_BF16 ? launch_attention_fwd_stream_t<bf16_t>(qkv, B, N, heads, dh, o, lse, scale, s) : launch_attention_fwd_stream_t<half_t>(qkv, B, N, heads, dh, o, lse, scale, s);
+  return M3_B16(launch_attention_fwd_stream_t, qkv, B, N, heads, dh, o, lse, scale, s);
 }
-
 int launch_attention_bwd_stream(int dtype, const void *qkv, const void *o, const void *d_o, const float *lse, int B, int N, int heads, int dh, void *dqkv, float *dq_ws, float scale, hipStream_t s) {
-  return dtype == M3_BF16 ? launch_attention_bwd_stream_t<bf16_t>(qkv, o, d_o, lse, B, N, heads, dh, dqkv, dq_ws, scale, s) : launch_attention_bwd_stream_t<half_t>(qkv, o, d_o, lse, B, N, heads, dh, dqkv, dq_ws, scale, s);
+  return M3_B16(launch_attention_bwd_stream_t, qkv, o, d_o, lse, B, N, heads, dh, dqkv, dq_ws, scale, s);
 }
-
 int launch_attention_fwd_res(int dtype, const void *qkv, int B, int N, int heads, int dh, void *o, float *lse, float scale, hipStream_t s) {
-  return dtype == M3_BF16 ? launch_attention_fwd_res_t<bf16_t>(qkv, B, N, heads, dh, o, lse, scale, s) : launch_attention_fwd_res_t<half_t>(qkv, B, N, heads, dh, o, lse, scale, s);
+  return M3_B16(launch_attention_fwd_res_t, qkv, B, N, heads, dh, o, lse, scale, s);
 }
-
 int launch_attention_bwd_res(int dtype, const void *qkv, const void *o, const void *d_o, const float *lse, int B, int N, int heads, int dh, void *dqkv, float scale, hipStream_t s) {
-  return dtype == M3_BF16 ? launch_attention_bwd_res_t<bf16_t>(qkv, o, d_o, lse, B, N, heads, dh, dqkv, scale, s) : launch_attention_bwd_res_t<half_t>(qkv, o, d_o, lse, B, N, heads, dh, dqkv, scale, s);
+  return M3_B16(launch_attention_bwd_res_t, qkv, o, d_o, lse, B, N, heads, dh, dqkv, scale, s);
 }
+#undef M3_B16
 
 }  // namespace m3
 

@@ -43,9 +43,9 @@ def heads(t, B, N, h, dh, parts):
     return [x[i] for i in range(parts)]
 
 
-# LDS-resident kernels (attention_res.hip): forward key tiles nkt = 4 * ceil(tiles / 4), backward tiles per wave kte.
+# LDS-resident kernels (attention_b16.hip, 16-bit dtypes): forward key tiles nkt = 4 * ceil(tiles / 4), backward tiles per wave kte.
 #   dh 32: N 64 (nkt 4, kte 1), 120 (8, 2), 180 (12, 3), 256 (16, 4);  dh 64: N 50 (4, 1), 100 (8, 1), 180 (12, 2), 256 (16, 2)
-# streamed kernels: N 257, 1025, 1201
+# streamed 16-bit kernels (same file): N 257, 1025, 1201; fp32 takes attention_f32.hip at every N
 SHAPES = [(2, 64, 2, 32), (1, 120, 1, 32), (1, 180, 2, 32), (1, 256, 1, 32), (1, 50, 1, 64), (2, 100, 1, 64),
           (1, 180, 1, 64), (1, 256, 1, 64), (1, 257, 2, 32), (1, 1025, 1, 64), (1, 1201, 1, 32)]
 
