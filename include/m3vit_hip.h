@@ -322,13 +322,13 @@ typedef struct {
 } m3_wgrad_plan_out;
 int m3_wgrad_plan(const m3_wgrad_shape *shape, m3_wgrad_plan_out *plan);
 /* Tuning knob, no reference counterpart: which weight-gradient launches take the LDS-DMA kernel (wgrad_dma_kernel,
- * csrc/wgrad.hip: four workgroups per CU, operands global -> LDS directly; fp16 / bf16 / fp32, power-of-two gather divisors, a
+ * csrc/wgrad_dma.hip: four workgroups per CU, operands global -> LDS directly; fp16 / bf16 / fp32, power-of-two gather divisors, a
  * per-row factor with fp16 / fp32 only).  0 = none (the register-staged kernel everywhere), 2 = every launch the kernel can
  * run, 1 (default) = those where it measured faster with operands streamed from HBM: fp32 always; 16-bit when tiles x groups
  * >= 1024 (one part per group: the ViT-Base experts) or N * K >= 1.5 M elements.  -1 = re-read M3_WGRAD_DMA.  Same results up to
  * fp32 summation order (64 instead of 32 contraction rows per accumulation step in 16 bit). */
 int m3_wgrad_set_dma(int on);
-/* Tuning knob, no reference counterpart: 256 x 256 output tiles (wgrad_big_kernel, csrc/wgrad.hip: eight waves, one workgroup
+/* Tuning knob, no reference counterpart: 256 x 256 output tiles (wgrad_big_kernel, csrc/wgrad_dma.hip: eight waves, one workgroup
  * per CU, two LDS stages filled by LDS-DMA) for 16-bit weights whose N and K are multiples of 256 - the ViT-Base shapes (768,
  * 2304, 3072).  1 = on (default), 0 = 128 x 128 everywhere, -1 = re-read M3_WGRAD_BIG.  m3_wgrad_tile reports (256, 256) for the
  * shapes it takes; switch before sizing workspaces.  Same results up to fp32 summation order. */
@@ -339,7 +339,7 @@ int m3_wgrad_tile(int N, int K, int dtype, int *tn, int *tk);
 /* 1 when m3_wgrad_tn runs a plain call of this shape (one group, no gathers / factor / bias / balanced units / direct mode) with
  * the streaming kernel for K = 16 / 32 - the router's weight, dW_gate = h^T d_logits (custom_moe_layer.py:213-217) - instead of
  * a 128 x 128 MFMA tile padded eightfold: m3_wgrad_plan then sizes `splits` for a stream over dC.  Slab layout and reduction
- * are unchanged.  M3_WGRAD_SKINNY=0 switches it off. */
+ * are unchanged.  The rule is fixed: it depends on the shape only. */
 int m3_wgrad_skinny(int N, int K, int G);
 /* balanced mode: dW[g] (+)= sum over group g's units of ws[u] (elems = N*K per group), unit order; optionally the
  * same for the bias slabs (bias_elems = N per group) */

@@ -1,0 +1,274 @@
+// The register-staged weight-gradient kernel (wgrad_tn_kernel) and its launcher; wgrad.hip describes the call.  Compiled as part of
+// wgrad_tiles.hip.
+// Both operands are row-major with the contraction index as the ROW, so fragments must
+// be read transposed out of LDS:
+//   f16: ds_read_b64_tr_b16 (4 rows x 16 cols per 16-lane group) on a [32][128]+pad
+//        image, row stride 288 B -> the 8 rows one 32-lane half touches land on
+//        8 disjoint 8-bank windows (conflict free);
+//   f32: ds_read_b32 (each lane one element) on a 528 B stride image (conflict free).
+// 128(n) x 128(k) output tile per 256-thread workgroup (2x2 waves of 64x64), 32 rows per
+// barrier step, double-buffered register staging.  Rows are split `splits` ways;
+// each split writes an fp32 slab, m3_wgrad_reduce adds the slabs in a fixed order
+// (deterministic, unlike atomics).
+#include "wgrad_dev.h"
+
+namespace m3 {
+
+template <typename T> struct WgLds;
+// ROWS: contraction rows per barrier step.  (fp16 with 64 rows - 32 MFMAs per wave per barrier instead of 16 - was
+// built in round 2: the second pair of staging registers spills, 256 VGPRs + 172 B scratch, and the step got 1-2 %
+// slower.)
+template <> struct WgLds<half_t> { static constexpr int STRIDE = 288; static constexpr int ROWS = 32; };
+template <> struct WgLds<bf16_t> { static constexpr int STRIDE = 288; static constexpr int ROWS = 32; };
+template <> struct WgLds<float> { static constexpr int STRIDE = 528; static constexpr int ROWS = 32; };
+
+// fragment for 16 columns starting at byte column offset colb (col*sizeof(T)) of the
+// LDS image `base`, contraction rows rb .. rb+KC-1
+template <typename T>
+__device__ __forceinline__ typename Mma<T>::frag read_tr_frag(const char *base, int rb, int col, int li, int lg);
+
+template <>
+__device__ __forceinline__ f16x8 read_tr_frag<half_t>(const char *base, int rb, int col, int li, int lg) {
+  // lane li of group lg supplies the address of (row 4*lg + (li>>2) [+16], cols col + 4*(li&3))
+  const char *p0 = base + (rb + 4 * lg + (li >> 2)) * WgLds<half_t>::STRIDE + (col + 4 * (li & 3)) * 2;
+  const char *p1 = p0 + 16 * WgLds<half_t>::STRIDE;
+  return wgrad_tr16_frag(p0, p1);
+}
+
+template <>
+__device__ __forceinline__ bf16x8 read_tr_frag<bf16_t>(const char *base, int rb, int col, int li, int lg) {
+  // the 16-bit transposed read does not look at the element format: same addressing as f16, bits re-labelled
+  return __builtin_bit_cast(bf16x8, read_tr_frag<half_t>(base, rb, col, li, lg));
+}
+
+template <>
+__device__ __forceinline__ f32x4 read_tr_frag<float>(const char *base, int rb, int col, int li, int lg) {
+  const char *p = base + (rb + 4 * lg) * WgLds<float>::STRIDE + (col + li) * 4;
+  f32x4 f;
+  f[0] = *(const float *)(p);
+  f[1] = *(const float *)(p + WgLds<float>::STRIDE);
+  f[2] = *(const float *)(p + 2 * WgLds<float>::STRIDE);
+  f[3] = *(const float *)(p + 3 * WgLds<float>::STRIDE);
+  return f;
+}
+
+template <typename T, bool GC, bool GA, bool SC = false>
+__global__ __launch_bounds__(WG_THREADS, 2) void wgrad_tn_kernel(const WgradDev p) {
+  typedef Mma<T> MM;
+  typedef typename MM::frag frag;
+  constexpr int ES = (int)sizeof(T);
+  constexpr int EPC = 16 / ES;
+  constexpr int STRIDE = WgLds<T>::STRIDE;
+  constexpr int ROWS = WgLds<T>::ROWS;                      // contraction rows per step
+  constexpr int CPR = WG_T * ES / 16;                       // 16-byte chunks per tile row
+  constexpr int NLD = ROWS * CPR / WG_THREADS;           // chunks per thread per operand
+  constexpr int RSTEP = WG_THREADS / CPR;                   // tile rows between a thread's chunks
+  constexpr int OPB = ROWS * STRIDE;                     // bytes per operand image
+  constexpr int KCH = ROWS / MM::KC;                     // fragment chunks per step
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int li = lane & 15, lg = lane >> 4;
+  const int wr = wave >> 1, wc = wave & 1;
+
+  // XCD-aware order: all tiles of one (group, split) read the SAME rows of dC and A (each byte is
+  // needed by tiles_k resp. tiles_n workgroups), so they are given consecutive logical ids, which the
+  // remap places on one XCD: the re-reads hit that XCD's L2 instead of the fabric.
+  const int tiles = gridDim.x;
+  int bz, gz;
+  if (wgrad_ride_along(p, tid, bz, gz)) return;
+  const int lin = blockIdx.x + tiles * (blockIdx.y + gridDim.y * bz);
+  int tile, gs, g, sp, nst;
+  int64_t r0, r1, s_begin;
+  if (p.chunk_rows) {                          // gs = work unit; its slab is ws[gs]
+    if (!wgrad_unit(p.group_offsets, p.G, p.chunk_rows, lin, tiles, lane, tile, gs, g, r0, r1)) return;
+    sp = gs; s_begin = 0;
+    nst = (int)((r1 - r0 + ROWS - 1) / ROWS);
+  } else {
+    const int log_id = xcd_remap(lin, tiles * gridDim.y * gz);
+    tile = log_id % tiles; gs = log_id / tiles;
+    g = gs % (int)gridDim.y; sp = gs / (int)gridDim.y;
+    if (p.group_offsets && p.lpt) g = wgrad_lpt_group(p.group_offsets, p.G, g, lane);
+    if (p.group_offsets) { r0 = p.group_offsets[g]; r1 = p.group_offsets[g + 1]; }
+    else { r0 = 0; r1 = p.M; }
+    const int64_t nsteps_all = (r1 - r0 + ROWS - 1) / ROWS;
+    const int64_t per = (nsteps_all + p.splits - 1) / p.splits;
+    s_begin = (int64_t)sp * per;
+    int64_t s_end = s_begin + per;
+    if (s_end > nsteps_all) s_end = nsteps_all;
+    nst = (int)(s_end > s_begin ? s_end - s_begin : 0);
+  }
+  const int tn = tile / p.tiles_k, tk = tile - tn * p.tiles_k;
+  const int n0 = tn * WG_T, k0 = tk * WG_T;
+  // slab / bias slab of this workgroup
+  const int64_t slab_id = p.chunk_rows ? (int64_t)sp : (int64_t)sp * p.G + g;
+
+  f32x4 acc[4][4];   // [ki][ni]: MFMA rows = k, cols = n
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // staging assignment: chunk i of this thread is tile row (tid / CPR) + RSTEP*i, 16-byte column c.
+  // Columns beyond N / K are clamped (they only feed outputs that are never stored); rows beyond the
+  // end of the group are clamped for the load and ZEROED at the LDS store (they would otherwise add
+  // into every output).  Loads are unconditional so hipcc's counted vmcnt waits stay exact.
+  const int srow = tid / CPR, c = tid - srow * CPR;
+  int ncol = n0 + c * EPC, kcol = k0 + c * EPC;
+  if (ncol > p.N - EPC) ncol = p.N - EPC;
+  if (kcol > p.K - EPC) kcol = p.K - EPC;
+  const char *c_base = p.dC + (int64_t)ncol * ES;
+  const char *a_base = p.A + (int64_t)kcol * ES;
+  const int st_off = srow * STRIDE + c * 16;                // + i*RSTEP*STRIDE
+  const int64_t rbase = r0 + s_begin * ROWS + srow;      // row of chunk 0 in local step 0
+
+  auto row_of = [&](int step, int i) -> int64_t {           // clamped slot row
+    int64_t m = rbase + (int64_t)step * ROWS + i * RSTEP;
+    return m < r1 ? m : r1 - 1;
+  };
+  auto load_index = [&](int step, int32_t(&ic)[NLD], int32_t(&ia)[NLD]) {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int64_t m = row_of(step, i);
+      if (GC) ic[i] = p.c_row_idx[m];
+      if (GA) ia[i] = p.a_row_idx[m];
+    }
+  };
+  // SC: the per-row factor travels with the row's data (loaded next to it, applied at the LDS store)
+  auto load_global = [&](int step, const int32_t(&ic)[NLD], const int32_t(&ia)[NLD], u32x4(&rc)[NLD], u32x4(&ra)[NLD],
+                         float(&rs)[NLD]) {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int64_t m = row_of(step, i);
+      const int64_t cr = GC ? (int64_t)div_by(ic[i], p.c_row_div, p.c_row_sh) : m;
+      const int64_t ar = GA ? (int64_t)div_by(ia[i], p.a_row_div, p.a_row_sh) : m;
+      rc[i] = *(const u32x4 *)(c_base + cr * p.lddc_b);
+      ra[i] = *(const u32x4 *)(a_base + ar * p.lda_b);
+      if (SC) rs[i] = p.c_row_scale[ic[i]];
+    }
+  };
+  auto store_lds = [&](int buf, int step, const u32x4(&rc)[NLD], const u32x4(&ra)[NLD], const float(&rs)[NLD]) {
+    char *base = smem + buf * (2 * OPB) + st_off;
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const bool ok = rbase + (int64_t)step * ROWS + i * RSTEP < r1;
+      const u32x4 cv = SC ? scale_chunk<T>(rc[i], rs[i]) : rc[i];
+      *(u32x4 *)(base + i * RSTEP * STRIDE) = ok ? cv : u32x4{0u, 0u, 0u, 0u};
+      *(u32x4 *)(base + i * RSTEP * STRIDE + OPB) = ok ? ra[i] : u32x4{0u, 0u, 0u, 0u};
+    }
+  };
+  // Bias gradient fused as one extra MFMA row: with an all-ones A operand the product is the column
+  // sum of dC over the contraction rows.  Done once per n-tile (k-tile 0, waves wr == 0).
+  const bool do_bias = (p.bias_ws || p.direct_db) && tk == 0 && wr == 0;
+  f32x4 acc_b[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) acc_b[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  frag ones;
+#pragma unroll
+  for (int j = 0; j < MM::EPL; ++j) ones[j] = (T)1.0f;
+
+  auto compute = [&](int buf) {
+    const char *sC = smem + buf * (2 * OPB), *sA = sC + OPB;
+#pragma unroll
+    for (int kc = 0; kc < KCH; ++kc) {
+      frag fk[4], fn[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        fk[i] = read_tr_frag<T>(sA, kc * MM::KC, wr * 64 + i * 16, li, lg);
+        fn[i] = read_tr_frag<T>(sC, kc * MM::KC, wc * 64 + i * 16, li, lg);
+      }
+#pragma unroll
+      for (int ki = 0; ki < 4; ++ki)
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) acc[ki][ni] = MM::mma(fk[ki], fn[ni], acc[ki][ni]);
+      if (do_bias) {
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) acc_b[ni] = MM::mma(ones, fn[ni], acc_b[ni]);
+      }
+    }
+  };
+
+  if (nst > 0) {
+    // prefetch distance 2 for the data (two register sets), 3 for the gather indices; steps past the
+    // end re-load the last step (clamped) so that nothing in the steady-state loop is conditional.
+    const int last = nst - 1;
+    auto cl = [&](int s_) { return s_ < last ? s_ : last; };
+    u32x4 rc0[NLD], ra0[NLD], rc1[NLD], ra1[NLD];
+    float sc0[NLD], sc1[NLD];
+    int32_t ic[NLD], ia[NLD];
+    load_index(0, ic, ia);
+    load_global(0, ic, ia, rc1, ra1, sc1);
+    load_index(cl(1), ic, ia);
+    load_global(cl(1), ic, ia, rc0, ra0, sc0);
+    load_index(cl(2), ic, ia);
+    store_lds(0, 0, rc1, ra1, sc1);
+    __syncthreads();
+    // entry of even local step t: buf0 = tile t, set0 = tile t+1, (ic, ia) = indices of tile t+2
+    int t = 0;
+    for (; t + 3 < nst; t += 2) {
+      load_global(t + 2, ic, ia, rc1, ra1, sc1);
+      load_index(cl(t + 3), ic, ia);
+      __builtin_amdgcn_sched_barrier(0);
+      compute(0);
+      store_lds(1, t + 1, rc0, ra0, sc0);
+      __syncthreads();
+      load_global(t + 3, ic, ia, rc0, ra0, sc0);
+      load_index(cl(t + 4), ic, ia);
+      __builtin_amdgcn_sched_barrier(0);
+      compute(1);
+      store_lds(0, t + 2, rc1, ra1, sc1);
+      __syncthreads();
+    }
+    const int rem = nst - t;
+    if (rem == 3) {
+      load_global(t + 2, ic, ia, rc1, ra1, sc1);
+      compute(0);
+      store_lds(1, t + 1, rc0, ra0, sc0);
+      __syncthreads();
+      compute(1);
+      store_lds(0, t + 2, rc1, ra1, sc1);
+      __syncthreads();
+      compute(0);
+    } else if (rem == 2) {
+      compute(0);
+      store_lds(1, t + 1, rc0, ra0, sc0);
+      __syncthreads();
+      compute(1);
+    } else {
+      compute(0);
+    }
+  }
+
+  if (do_bias && lg == 0) {                       // every row of the ones-product is the column sum: take row 0
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni) {
+      const int n = n0 + wc * 64 + ni * 16 + li;
+      if (n < p.N) wgrad_store_bias(p, acc_b[ni][0], slab_id, g, n);
+    }
+  }
+  wgrad_store_tile(p, acc, slab_id, g, n0, k0, wr, wc, li, lg);
+}
+
+// the instances: every dtype with every pair of gathers; a per-row factor only on gathered dC rows
+struct WgStaged {
+  template <typename T, bool GC, bool GA, bool SC> static const void *instance() {
+    if constexpr (!SC || GC) return (const void *)wgrad_tn_kernel<T, GC, GA, SC>;
+    else return nullptr;
+  }
+};
+
+int launch_wgrad_staged(int dtype, bool gc, bool ga, bool sc, dim3 grid, const WgradDev &d, hipStream_t s) {
+  const size_t lds16 = 4 * WgLds<half_t>::ROWS * WgLds<half_t>::STRIDE, lds32 = 4 * WgLds<float>::ROWS * WgLds<float>::STRIDE;
+  static bool attr_set = false;
+  if (!attr_set) {                               // both images exceed the 64 KiB a launch gets without asking
+    wgrad_each_instance<WgStaged>([&](int dt, bool, bool, bool, const void *k) {
+      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(dt == M3_F32 ? lds32 : lds16));
+    });
+    attr_set = true;
+  }
+  return wgrad_launch_instance<WgStaged>(dtype, gc, ga, sc, grid, dim3(WG_THREADS), dtype == M3_F32 ? lds32 : lds16, d, s);
+}
+
+}  // namespace m3

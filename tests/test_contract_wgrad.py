@@ -176,11 +176,12 @@ def test_wgrad_kernels_and_slab_splits(ops, kern, splits):
 
 
 @pytest.mark.parametrize("splits", [None, 1, 4])
-@pytest.mark.parametrize("kern", ["staged_f16", "dma_f16", "dma_f32", "big_f16"])
+@pytest.mark.parametrize("kern", ["staged_f16", "dma_f16", "dma_f32", "big_f16", "dma_bf16", "big_bf16"])
 def test_wgrad_grouped_balanced_and_direct(ops, kern, splits):
     """grouped: an empty first / middle / last expert and one hot one (balanced units give it more workgroups), slack rows
     past group_offsets[G]; rows gathered (a_row_idx / 2) and dC read through the combine's slot map (c_row_idx / k = 2) scaled
-    by the gate score"""
+    by the gate score.  bf16 rows with a per-row factor are the one call both LDS-DMA kernels must refuse (the 256 x 256
+    kernel has the factor for fp16 only, the 128-wide one for fp16 and fp32): it has to land on the register-staged kernel"""
     dtype, N, K, dma, big, _ = KERNELS[kern]
     counts = [0, 700, 0, 45, 129, 0]
     G, M = len(counts), sum(counts) + 19

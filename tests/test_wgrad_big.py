@@ -1,4 +1,4 @@
-"""GPU: the 256 x 256 weight-gradient kernel (wgrad_big_kernel, csrc/wgrad.hip: 16-bit ViT-Base shapes) against torch fp64 on
+"""GPU: the 256 x 256 weight-gradient kernel (wgrad_big_kernel, csrc/wgrad_dma.hip: 16-bit ViT-Base shapes) against torch fp64 on
 the same rounded operands and against the 128 x 128 kernels on the same call: dense with row splits and ragged tails, a unit
 of ONE step, grouped experts with gathered dC / gathered A rows, ragged and EMPTY experts, the gate score on the rows, the
 fused bias sums, slabs and direct accumulation, the balanced (chunked) units, and the queue around it."""

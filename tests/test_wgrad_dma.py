@@ -1,4 +1,4 @@
-"""GPU: the LDS-DMA weight-gradient kernel (wgrad_dma_kernel, csrc/wgrad.hip: fp16 / bf16 / fp32 operands, no per-row factor) against
+"""GPU: the LDS-DMA weight-gradient kernel (wgrad_dma_kernel, csrc/wgrad_dma.hip: fp16 / bf16 / fp32 operands, no per-row factor) against
 torch fp64 on the same rounded operands and against the register-staged kernel on the same call: dense with row splits,
 ragged unit tails (rows past a unit's end read the zero row), partial column tiles, grouped with ragged and EMPTY experts,
 gathered dC rows (expert FC2: token-major d y), gathered A rows with a power-of-two divisor (expert FC1: tokens through
