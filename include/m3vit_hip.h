@@ -298,8 +298,58 @@ typedef struct {
                                       experts: 151 MB per layer), where slabs + reduction move four times the result. */
   float *direct_db;                /* direct mode, optional: the bias gradient [G][N] (column sums of dC) likewise */
   int32_t direct_beta, direct_beta_db;
+  int32_t n_prev;                  /* > 1: prev points to that many descriptors - what one m3_wgrad_multi call left behind
+                                      (its reduce_out): dense reductions of the same number of slabs.  0 / 1: one descriptor.
+                                      In direct mode no prev reduction may write direct_dW / direct_db: the call is refused
+                                      (this launch read-add-writes them while the reduce blocks run). */
 } m3_wgrad_args;
 int m3_wgrad_tn(const m3_wgrad_args *args, void *stream);
+/* Several dense weight gradients over the SAME M rows in one launch - the dense weights of one transformer block's backward
+ * (qkv, proj, fc1, fc2), whose operands all exist once the attention backward has run:
+ *   dW_j[n, k] (+)= sum_m dC_j[m, n] * A_j[m, k],   db_j[n] (+)= sum_m dC_j[m, n]      j < n <= M3_WGRAD_MULTI_MAX
+ * Plain rows only (no gathers, no per-row factor, one group), 16-bit operands, and every (N_j, K_j) a shape m3_wgrad_tn gives
+ * to its register-staged 128 x 128 kernel under the current m3_wgrad_set_dma / m3_wgrad_set_big settings: m3_wgrad_multi_plan
+ * reports `allowed`, and a caller whose batch is not keeps the call per weight.  All problems are cut into the same `parts`
+ * row parts (m3_wgrad_multi_plan: the fewest that fill 432 workgroups without exceeding the 512 resident ones, at most 16, at
+ * least 16 32-row steps each), every part of every tile writes one fp32 slab into ws (ws_elems floats: problem j's weight slabs
+ * [parts][N_j][K_j] at ws_off[j], its bias slabs [parts][N_j] at bias_off[j]), and the slabs are summed in part order:
+ * deterministic, no atomics.  The call does not sum them itself: it fills reduce_out[0 .. n) with the n reductions, which the
+ * NEXT m3_wgrad_tn / m3_wgrad_multi call of the stream carries out in front of its own work (prev = reduce_out, n_prev = n)
+ * or m3_wgrad_reduce_multi launches.  prev as in m3_wgrad_args (slabs outside this call's ws); a prev reduction that writes a
+ * dW / db of this call is refused, and so are two problems with the same dW / db.
+ * Same results as the calls one by one up to fp32 summation order (other row parts). */
+#define M3_WGRAD_MULTI_MAX 8
+typedef struct {
+  const void *dC; int64_t lddc;    /* [M, N], row stride in elements */
+  const void *A; int64_t lda;      /* [M, K] */
+  int32_t N, K;
+  float *dW; float *db;            /* fp32 [N, K]; [N] or NULL; 16-byte aligned */
+  int32_t beta, beta_db;           /* 1: accumulate */
+} m3_wgrad_problem;
+typedef struct {
+  int64_t M; int32_t dtype; int32_t n;
+  int32_t parts;                   /* 0: the library's rule; >= 1: the caller's row parts */
+  int32_t N[M3_WGRAD_MULTI_MAX], K[M3_WGRAD_MULTI_MAX], bias[M3_WGRAD_MULTI_MAX];
+} m3_wgrad_multi_shape;
+typedef struct {
+  int32_t allowed;                 /* 0: m3_wgrad_multi refuses this batch */
+  int32_t parts, tiles, workgroups; /* row parts, 128 x 128 tiles of all problems, parts * tiles */
+  int64_t ws_elems;
+  int64_t ws_off[M3_WGRAD_MULTI_MAX], bias_off[M3_WGRAD_MULTI_MAX];
+} m3_wgrad_multi_plan_out;
+int m3_wgrad_multi_plan(const m3_wgrad_multi_shape *shape, m3_wgrad_multi_plan_out *plan);
+typedef struct {
+  int64_t M; int32_t dtype; int32_t n;
+  m3_wgrad_problem prob[M3_WGRAD_MULTI_MAX];
+  int32_t parts;                   /* as in m3_wgrad_multi_shape */
+  float *ws;                       /* m3_wgrad_multi_plan's ws_elems floats, 16-byte aligned */
+  const m3_wgrad_reduce_desc *prev; int32_t n_prev;
+  m3_wgrad_reduce_desc *reduce_out; /* [n], host memory, written during the call */
+} m3_wgrad_multi_args;
+int m3_wgrad_multi(const m3_wgrad_multi_args *args, void *stream);
+/* n == 1: m3_wgrad_reduce / m3_wgrad_reduce_grouped of the descriptor; n > 1: the reductions one m3_wgrad_multi call left
+ * behind, in one launch */
+int m3_wgrad_reduce_multi(const m3_wgrad_reduce_desc *descs, int n, void *stream);
 /* How to cut a call up: fill m3_wgrad_shape, call m3_wgrad_plan (host code, no GPU work), copy splits / chunk_rows / units into
  * m3_wgrad_args and give the call ws_elems floats of workspace (weight slabs first, then the bias slabs).  The plan follows the
  * kernel m3_wgrad_tn takes for the shape under the current m3_wgrad_set_dma / m3_wgrad_set_big settings: the streaming kernel

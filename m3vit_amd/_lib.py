@@ -65,6 +65,7 @@ class WgradArgs(Structure):
         ("c_row_div", c_int32), ("c_row_scale", c_void_p),
         ("prev", POINTER(WgradReduceDesc)),
         ("direct_dW", c_void_p), ("direct_db", c_void_p), ("direct_beta", c_int32), ("direct_beta_db", c_int32),
+        ("n_prev", c_int32),
     ]
 
 
@@ -75,6 +76,30 @@ class WgradShape(Structure):
 
 class WgradPlan(Structure):
     _fields_ = [("splits", c_int32), ("chunk_rows", c_int32), ("units", c_int32), ("direct", c_int32), ("ws_elems", c_int64)]
+
+
+WGRAD_MULTI_MAX = 8
+
+
+class WgradProblem(Structure):
+    _fields_ = [("dC", c_void_p), ("lddc", c_int64), ("A", c_void_p), ("lda", c_int64), ("N", c_int32), ("K", c_int32),
+                ("dW", c_void_p), ("db", c_void_p), ("beta", c_int32), ("beta_db", c_int32)]
+
+
+class WgradMultiShape(Structure):
+    _fields_ = [("M", c_int64), ("dtype", c_int32), ("n", c_int32), ("parts", c_int32),
+                ("N", c_int32 * WGRAD_MULTI_MAX), ("K", c_int32 * WGRAD_MULTI_MAX), ("bias", c_int32 * WGRAD_MULTI_MAX)]
+
+
+class WgradMultiPlan(Structure):
+    _fields_ = [("allowed", c_int32), ("parts", c_int32), ("tiles", c_int32), ("workgroups", c_int32), ("ws_elems", c_int64),
+                ("ws_off", c_int64 * WGRAD_MULTI_MAX), ("bias_off", c_int64 * WGRAD_MULTI_MAX)]
+
+
+class WgradMultiArgs(Structure):
+    _fields_ = [("M", c_int64), ("dtype", c_int32), ("n", c_int32), ("prob", WgradProblem * WGRAD_MULTI_MAX),
+                ("parts", c_int32), ("ws", c_void_p), ("prev", POINTER(WgradReduceDesc)), ("n_prev", c_int32),
+                ("reduce_out", POINTER(WgradReduceDesc))]
 
 
 class CastDesc(Structure):
@@ -137,6 +162,9 @@ SIGNATURES = {
     "m3_gemm_set_big": (c_int, [_I]),
     "m3_wgrad_tn": (c_int, [POINTER(WgradArgs), _V]),
     "m3_wgrad_plan": (c_int, [POINTER(WgradShape), POINTER(WgradPlan)]),
+    "m3_wgrad_multi_plan": (c_int, [POINTER(WgradMultiShape), POINTER(WgradMultiPlan)]),
+    "m3_wgrad_multi": (c_int, [POINTER(WgradMultiArgs), _V]),
+    "m3_wgrad_reduce_multi": (c_int, [POINTER(WgradReduceDesc), _I, _V]),
     "m3_wgrad_tile": (c_int, [_I, _I, _I, POINTER(c_int), POINTER(c_int)]),
     "m3_wgrad_skinny": (c_int, [_I, _I, _I]),
     "m3_wgrad_set_dma": (c_int, [_I]),

@@ -9,7 +9,8 @@
 //
 // This file: the entry points, the launch plan, the choice of the kernel that takes a call, the slab reductions, the column
 // sums and the streaming kernel for the router's weight.  The tile kernels live with their launchers in wgrad_staged.hip
-// (register-staged, 128 x 128) and wgrad_dma.hip (LDS-DMA, 128 x 128 and 256 x 256), both compiled through wgrad_tiles.hip; wgrad_dev.h holds what they share.
+// (register-staged, 128 x 128), wgrad_multi.hip (several dense weights in one launch) and wgrad_dma.hip (LDS-DMA, 128 x 128 and
+// 256 x 256), all compiled through wgrad_tiles.hip; wgrad_dev.h holds what they share.
 #include "wgrad_dev.h"
 #include <algorithm>
 
@@ -111,6 +112,12 @@ __global__ __launch_bounds__(256) void wgrad_reduce_grouped_kernel(const float *
                                                                    float *dW, int beta, int nb_w, const float *bias_ws, int64_t belems4,
                                                                    float *db, int beta_db) {
   wgrad_reduce_grouped_block(blockIdx.x, blockIdx.y, threadIdx.x, ws, off, G, chunk, elems4, dW, beta, nb_w, bias_ws, belems4, db, beta_db);
+}
+
+// the reductions a batched launch leaves behind (p.rd_n > 1, WgradDev.rd_tab0 ..) as a launch of their own: every block a reduce block
+__global__ __launch_bounds__(256) void wgrad_reduce_multi_kernel(const WgradDev p) {
+  int bz, gz;
+  (void)wgrad_ride_along(p, threadIdx.x, bz, gz);
 }
 
 // ------------------------------------------------------------------ column sums
@@ -340,6 +347,74 @@ extern "C" int m3_wgrad_bias_reduce(const float *bias_ws, int splits, int64_t el
   return launch_reduce_rows_f32(bias_ws, splits, (int)elems, 1, 0, db, beta, (hipStream_t)stream);
 }
 
+// The reductions of a batched launch (m3_wgrad_multi: n > 1 dense descriptors of the same number of slabs) as the kernels take
+// them: WgradDev.rd_tab0 .., the reduce blocks of problem after problem
+static int wgrad_fill_rd_multi(WgradDev &d, const m3_wgrad_reduce_desc *r, int n, const char *who) {
+  M3_REQUIRE(n >= 2 && n <= WG_MULTI, "%s: %d reductions in one descriptor table (2 .. %d)", who, n, WG_MULTI);
+  WgradRdProb *tab = &d.rd_tab0;
+  int first = 0;
+  for (int j = 0; j < WG_MULTI; ++j) {
+    tab[j] = WgradRdProb{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, INT32_MAX, 0};
+    if (j >= n) continue;
+    M3_REQUIRE(wgrad_reduce_desc_ok(r[j]) && wgrad_reduce_bias_ok(r[j]) && r[j].chunk_rows == 0 && r[j].elems > 0 && r[j].splits == r[0].splits,
+               "%s: a table of reductions holds dense ones of the same number of slabs", who);
+    M3_REQUIRE(((uintptr_t)r[j].ws % 16) == 0 && ((uintptr_t)r[j].dW % 16) == 0 &&
+               (!r[j].bias_ws || (((uintptr_t)r[j].bias_ws % 16) == 0 && ((uintptr_t)r[j].db % 16) == 0)), "%s: reduction alignment", who);
+    const WgradReduceGeom g = wgrad_reduce_geom(r[j]);
+    tab[j] = WgradRdProb{r[j].ws, r[j].dW, r[j].bias_ws, r[j].db, g.e4, (int32_t)g.b4, g.nb_w, first, (r[j].beta ? 1 : 0) | (r[j].beta_db ? 2 : 0)};
+    first += g.nb_w + g.nb_b;
+  }
+  d.rd_n = n; d.rd_blocks = first; d.rd_nbx = first; d.rd_nbw = 0; d.rd_chunk = 0;
+  d.rd_splits = r[0].splits; d.rd_cols = m3_wgrad_reduce_cols(r[0].splits);
+  return M3_OK;
+}
+
+extern "C" int m3_wgrad_reduce_multi(const m3_wgrad_reduce_desc *descs, int n, void *stream) {
+  M3_REQUIRE(descs && n >= 1, "m3_wgrad_reduce_multi: bad args");
+  if (n == 1) return wgrad_reduce_launch(descs[0], (hipStream_t)stream);
+  WgradDev d = {};
+  if (int rc = wgrad_fill_rd_multi(d, descs, n, "m3_wgrad_reduce_multi")) return rc;
+  d.rd_zslices = 1;
+  hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3((unsigned)d.rd_blocks), dim3(256), 0, (hipStream_t)stream, d);
+  return check_launch("m3_wgrad_reduce_multi");
+}
+
+// The previous call's slab reduction(s) (prev[0 .. n_prev)) for a launch with the argument block d: into d.rd_*, to ride in
+// front of that launch - or, where the launch cannot carry them (own_launch), launched here
+static int wgrad_take_prev(WgradDev &d, const m3_wgrad_reduce_desc *prev, int n_prev, const float *ws, bool own_launch, hipStream_t s,
+                           const char *who) {
+  d.rd_blocks = 0; d.rd_zslices = 0; d.rd_cols = 256; d.rd_n = 0;
+  if (!prev) return M3_OK;
+  const int n = n_prev > 1 ? n_prev : 1;
+  M3_REQUIRE(n <= WG_MULTI, "%s: n_prev %d", who, n);
+  for (int j = 0; j < n; ++j) {
+    M3_REQUIRE(wgrad_reduce_desc_ok(prev[j]), "%s: bad prev reduce descriptor", who);
+    M3_REQUIRE(wgrad_reduce_bias_ok(prev[j]), "%s: prev bias slabs need db", who);
+    M3_REQUIRE(prev[j].ws != ws, "%s: prev slabs and this call's slabs must be different buffers", who);
+  }
+  if (n > 1) {
+    if (own_launch) return m3_wgrad_reduce_multi(prev, n, s);
+    return wgrad_fill_rd_multi(d, prev, n, who);
+  }
+  const m3_wgrad_reduce_desc *r = prev;
+  if (r->elems > 0) {
+    if (own_launch) return wgrad_reduce_launch(*r, s);
+    const WgradReduceGeom g = wgrad_reduce_geom(*r);
+    d.rd_cols = g.cols; d.rd_nbw = g.nb_w; d.rd_nbx = g.nb_w + g.nb_b;
+    d.rd_blocks = d.rd_nbx * (r->chunk_rows ? r->G : 1);
+    d.rd_ws = r->ws; d.rd_splits = r->splits; d.rd_e4 = g.e4; d.rd_off = r->group_offsets; d.rd_G = r->G; d.rd_chunk = r->chunk_rows;
+    d.rd_dW = r->dW; d.rd_beta = r->beta; d.rd_bws = r->bias_ws; d.rd_b4 = g.b4; d.rd_db = r->db; d.rd_beta_db = r->beta_db;
+  }
+  return M3_OK;
+}
+// the grid's leading z slices for the reduce blocks d carries
+static void wgrad_prev_slices(WgradDev &d, dim3 &grid) {
+  if (d.rd_blocks <= 0) return;
+  const int per_slice = (int)(grid.x * grid.y);
+  d.rd_zslices = (d.rd_blocks + per_slice - 1) / per_slice;
+  grid.z += d.rd_zslices;
+}
+
 // ------------------------------------------------------------------ the weight-gradient call
 // "The LDS-DMA form can run this call" (both wgrad_dma.hip kernels): power-of-two gather divisors (the kernels shift), every
 // operand row within the 32-bit offsets a lane adds to the operand base, and a per-row factor only on gathered rows of a
@@ -395,36 +470,20 @@ extern "C" int m3_wgrad_tn(const m3_wgrad_args *a, void *stream) {
   const bool gc = a->c_row_idx != nullptr, ga = a->a_row_idx != nullptr, sc = a->c_row_scale != nullptr;
   const WgradKernel kern = wgrad_demote(wgrad_kernel_of_shape(a->N, a->K, a->G, a->dtype), a, d);
   const bool big = kern == WGRAD_BIG;
-  // the previous call's slab reduction (a->prev): in front of this launch (128-wide kernels), or as its own launch
-  d.rd_blocks = 0; d.rd_zslices = 0; d.rd_cols = 256;
+  // the previous call's slab reduction (a->prev): in front of this launch (128-wide kernels), or as its own launch.  In direct
+  // mode this launch read-add-writes dW while those blocks run: they must not write the same tensor
+  const int n_prev = a->prev ? (a->n_prev > 1 ? a->n_prev : 1) : 0;
+  for (int j = 0; j < n_prev && a->direct_dW; ++j)
+    M3_REQUIRE(a->prev[j].dW != a->direct_dW && (!a->direct_db || a->prev[j].db != a->direct_db),
+               "m3_wgrad_tn: the prev reduction writes the dW / db this direct-mode launch adds into");
+  if (int rc = wgrad_take_prev(d, a->prev, a->n_prev, a->ws, big || a->M == 0, s, "m3_wgrad_tn")) return rc;
   static int lpt = -1;
   if (lpt < 0) { const char *e = getenv("M3_WGRAD_LPT"); lpt = e ? (atoi(e) ? 1 : 0) : 1; }
   d.lpt = lpt;
-  if (a->prev) {
-    const m3_wgrad_reduce_desc *r = a->prev;
-    M3_REQUIRE(wgrad_reduce_desc_ok(*r), "m3_wgrad_tn: bad prev reduce descriptor");
-    M3_REQUIRE(wgrad_reduce_bias_ok(*r), "m3_wgrad_tn: prev bias slabs need db");
-    M3_REQUIRE(r->ws != a->ws, "m3_wgrad_tn: prev slabs and this call's slabs must be different buffers");
-    if (r->elems > 0) {
-      if (big || a->M == 0) {
-        if (int rc = wgrad_reduce_launch(*r, s)) return rc;
-      } else {
-        const WgradReduceGeom g = wgrad_reduce_geom(*r);
-        d.rd_cols = g.cols; d.rd_nbw = g.nb_w; d.rd_nbx = g.nb_w + g.nb_b;
-        d.rd_blocks = d.rd_nbx * (r->chunk_rows ? r->G : 1);
-        d.rd_ws = r->ws; d.rd_splits = r->splits; d.rd_e4 = g.e4; d.rd_off = r->group_offsets; d.rd_G = r->G; d.rd_chunk = r->chunk_rows;
-        d.rd_dW = r->dW; d.rd_beta = r->beta; d.rd_bws = r->bias_ws; d.rd_b4 = g.b4; d.rd_db = r->db; d.rd_beta_db = r->beta_db;
-      }
-    }
-  }
   const int t = big ? BG_T : WG_T;
   d.tiles_k = (a->K + t - 1) / t;
   dim3 grid(((a->N + t - 1) / t) * d.tiles_k, a->chunk_rows ? a->units : a->G, a->chunk_rows ? 1 : a->splits);
-  if (d.rd_blocks > 0) {                         // leading z slices for the previous call's reduce blocks
-    const int per_slice = (int)(grid.x * grid.y);
-    d.rd_zslices = (d.rd_blocks + per_slice - 1) / per_slice;
-    grid.z += d.rd_zslices;
-  }
+  wgrad_prev_slices(d, grid);
   if (big) return launch_wgrad_big(a->dtype, gc, ga, sc, grid, d, s);
   if (kern == WGRAD_SKINNY) {                    // the router's weight (K = 16 / 32, plain rows): the streaming kernel
     for_dtype(a->dtype, [&](auto tag) {
@@ -436,6 +495,94 @@ extern "C" int m3_wgrad_tn(const m3_wgrad_args *a, void *stream) {
   }
   M3_REQUIRE(a->N * es >= 16 && a->K * es >= 16, "m3_wgrad_tn: N, K too small");
   return kern == WGRAD_DMA ? launch_wgrad_dma(a->dtype, gc, ga, sc, grid, d, s) : launch_wgrad_staged(a->dtype, gc, ga, sc, grid, d, s);
+}
+
+// ------------------------------------------------------------------ the batched weight-gradient call
+// One launch for several dense weight gradients over the same rows (wgrad_multi.hip).  Allowed where every problem is one the
+// register-staged kernel takes by today's rules, in 16 bit: fp32 and the shapes of the LDS-DMA and 256 x 256 kernels (ViT-Base)
+// keep their launch per weight.
+// Row parts: ONE count P for all problems, the smallest that fills 432 workgroups (what the qkv weight of configs[1] gets by
+// itself: 27 tiles x 16 parts; the slot sweep of profiles/r04_levers_measured_and_dropped.txt found 432 about level with all
+// 512 resident slots) - unless that spills over the 512 slots, where a few workgroups would run as a second round: then the
+// most parts that fit.  At most 16 parts, and at least 16 32-row steps per part, as for a single call.  Measured at M = 25 216,
+// 108 tiles (a dense block of configs[1]): P = 4 (432 workgroups) 148 us, P = 5 (540: a second round of 28) 188 us, P = 9 147 us
+// with more than twice the slab bytes (profiles/wgrad_multi_premise.txt).
+extern "C" int m3_wgrad_multi_plan(const m3_wgrad_multi_shape *s, m3_wgrad_multi_plan_out *p) {
+  M3_REQUIRE(s && p, "m3_wgrad_multi_plan: null argument");
+  M3_REQUIRE(dtype_ok(s->dtype) && s->n >= 1 && s->n <= M3_WGRAD_MULTI_MAX && s->M >= 0 && s->M < ((int64_t)1 << 31) && s->parts >= 0,
+             "m3_wgrad_multi_plan: bad shape");
+  *p = m3_wgrad_multi_plan_out{};
+  bool ok = s->dtype != M3_F32 && s->M > 0;
+  int64_t tiles = 0;
+  for (int j = 0; j < s->n; ++j) {
+    M3_REQUIRE(s->N[j] > 0 && s->K[j] > 0, "m3_wgrad_multi_plan: bad shape of problem %d", j);
+    ok = ok && wgrad_kernel_of_shape(s->N[j], s->K[j], 1, s->dtype) == WGRAD_STAGED;
+    tiles += (int64_t)((s->N[j] + WG_T - 1) / WG_T) * ((s->K[j] + WG_T - 1) / WG_T);
+  }
+  M3_REQUIRE(tiles <= (1 << 20), "m3_wgrad_multi_plan: %lld tiles", (long long)tiles);
+  int64_t P = s->parts;
+  if (!P) {
+    const int64_t steps = std::max<int64_t>(1, (s->M + 31) / 32), cap = std::min<int64_t>(16, std::max<int64_t>(1, steps / 16));
+    P = (432 + tiles - 1) / tiles;
+    if (P * tiles > 512) P = std::max<int64_t>(1, 512 / tiles);
+    P = std::min(P, cap);
+  }
+  M3_REQUIRE(P <= 4096, "m3_wgrad_multi_plan: %lld parts", (long long)P);
+  p->allowed = ok; p->parts = (int32_t)P; p->tiles = (int32_t)tiles; p->workgroups = (int32_t)(P * tiles);
+  int64_t off = 0;
+  for (int j = 0; j < s->n; ++j) { p->ws_off[j] = off; off += P * s->N[j] * s->K[j]; }
+  for (int j = 0; j < s->n; ++j) { p->bias_off[j] = off; off += s->bias[j] ? P * s->N[j] : 0; }
+  p->ws_elems = off;
+  return M3_OK;
+}
+
+extern "C" int m3_wgrad_multi(const m3_wgrad_multi_args *a, void *stream) {
+  M3_REQUIRE(a && a->ws && a->reduce_out, "m3_wgrad_multi: null argument");
+  M3_REQUIRE(a->n >= 1 && a->n <= M3_WGRAD_MULTI_MAX && a->parts >= 0, "m3_wgrad_multi: %d problems, %d parts", a->n, a->parts);
+  M3_REQUIRE(((uintptr_t)a->ws % 16) == 0, "m3_wgrad_multi: alignment");
+  m3_wgrad_multi_shape sh = {};
+  sh.M = a->M; sh.dtype = a->dtype; sh.n = a->n; sh.parts = a->parts;
+  for (int j = 0; j < a->n; ++j) { sh.N[j] = a->prob[j].N; sh.K[j] = a->prob[j].K; sh.bias[j] = a->prob[j].db != nullptr; }
+  m3_wgrad_multi_plan_out pl;
+  if (int rc = m3_wgrad_multi_plan(&sh, &pl)) return rc;
+  M3_REQUIRE(pl.allowed, "m3_wgrad_multi: this batch is not one m3_wgrad_multi_plan allows (16-bit, M > 0, shapes of the register-staged kernel)");
+  const int es = dtype_size(a->dtype);
+  const int n_prev = a->prev ? (a->n_prev > 1 ? a->n_prev : 1) : 0;
+  WgradMultiDev md = {};
+  WgradProb *tab = &md.tab0;
+  for (int j = 0; j < WG_MULTI; ++j) tab[j].first = INT32_MAX;
+  int first = 0;
+  for (int j = 0; j < a->n; ++j) {
+    const m3_wgrad_problem &q = a->prob[j];
+    M3_REQUIRE(q.dC && q.A && q.dW, "m3_wgrad_multi: null operand in problem %d", j);
+    M3_REQUIRE((q.N * es) % 16 == 0 && (q.K * es) % 16 == 0 && (q.lddc * es) % 16 == 0 && (q.lda * es) % 16 == 0 && q.lddc >= q.N && q.lda >= q.K,
+               "m3_wgrad_multi: problem %d: rows and N*elem, K*elem must be multiples of 16 bytes", j);
+    M3_REQUIRE(((uintptr_t)q.dC % 16) == 0 && ((uintptr_t)q.A % 16) == 0 && ((uintptr_t)q.dW % 16) == 0 && ((uintptr_t)q.db % 16) == 0,
+               "m3_wgrad_multi: problem %d: alignment", j);
+    for (int i = 0; i < j; ++i)
+      M3_REQUIRE(a->prob[i].dW != q.dW && (!q.db || a->prob[i].db != q.db), "m3_wgrad_multi: problems %d and %d write the same dW / db", i, j);
+    // the prev reductions run inside this launch, this launch's own after it: one that writes the same tensor would be a caller
+    // that accumulates into a gradient twice in a row - refused rather than ordered
+    for (int i = 0; i < n_prev; ++i)
+      M3_REQUIRE(a->prev[i].dW != q.dW && (!q.db || a->prev[i].db != q.db),
+                 "m3_wgrad_multi: the prev reduction writes the dW / db of problem %d", j);
+    const int tiles_k = (q.K + WG_T - 1) / WG_T;
+    float *bws = q.db ? a->ws + pl.bias_off[j] : nullptr;
+    tab[j] = WgradProb{(const char *)q.dC, q.lddc * es, (const char *)q.A, q.lda * es, a->ws + pl.ws_off[j], bws, q.N, q.K, tiles_k, first};
+    first += ((q.N + WG_T - 1) / WG_T) * tiles_k;
+    a->reduce_out[j] = m3_wgrad_reduce_desc{a->ws + pl.ws_off[j], pl.parts, (int64_t)q.N * q.K, nullptr, 1, 0, q.dW, q.beta ? 1 : 0,
+                                            bws, q.db ? (int64_t)q.N : 0, q.db, q.beta_db ? 1 : 0};
+  }
+  WgradDev &d = md.d;
+  d.M = a->M; d.G = 1; d.splits = pl.parts; d.a_row_div = 1; d.c_row_div = 1;
+  hipStream_t s = (hipStream_t)stream;
+  // slabs of the prev reductions: anywhere but in this launch's workspace
+  for (int i = 0; i < n_prev; ++i)
+    M3_REQUIRE(a->prev[i].ws < a->ws || a->prev[i].ws >= a->ws + pl.ws_elems, "m3_wgrad_multi: prev slabs inside this call's workspace");
+  if (int rc = wgrad_take_prev(d, a->prev, a->n_prev, a->ws, false, s, "m3_wgrad_multi")) return rc;
+  dim3 grid((unsigned)pl.tiles, 1, (unsigned)pl.parts);
+  wgrad_prev_slices(d, grid);
+  return launch_wgrad_multi(a->dtype, grid, md, s);
 }
 
 // ------------------------------------------------------------------ column sums

@@ -1,6 +1,6 @@
 // Shared by the weight-gradient sources (wgrad.hip: entry points, launch plan, kernel choice, slab reductions, column sums,
-// the streaming kernel; wgrad_staged.hip: the register-staged 128 x 128 kernel; wgrad_dma.hip: the LDS-DMA kernels, 128 x 128
-// and 256 x 256): the kernels' argument block, the work units of a grouped call, the result stores, the slab reduction that
+// the streaming kernel; wgrad_staged.hip: the register-staged 128 x 128 kernel; wgrad_multi.hip: the same over several weights
+// in one launch; wgrad_dma.hip: the LDS-DMA kernels, 128 x 128 and 256 x 256): the kernels' argument block, the work units of a grouped call, the result stores, the slab reduction that
 // rides in front of a launch, and the launchers wgrad.hip dispatches to.
 #pragma once
 #include "common.h"
@@ -12,6 +12,17 @@ constexpr int WG_T = 128;        // tile edge (n and k)
 constexpr int WG_ROWS = 64;      // granule of the row splits (= the largest per-dtype step below)
 constexpr int WG_THREADS = 256;
 constexpr int BG_T = 256, BG_THREADS = 512, BG_RS = 512;
+
+constexpr int WG_MULTI = 8;     // problems of one batched launch (M3_WGRAD_MULTI_MAX)
+
+// one of the dense slab reductions a batched launch leaves behind (WgradDev.rd_tab)
+struct WgradRdProb {
+  const float *ws; float *dW; const float *bws; float *db;
+  int64_t e4; int32_t b4;
+  int32_t nbw;                     // reduce blocks of the weight elements (the bias blocks follow them)
+  int32_t first;                   // the first reduce block of this problem; INT32_MAX in the unused entries
+  int32_t beta;                    // bit 0: dW += , bit 1: db +=
+};
 
 struct WgradDev {
   const char *dC; int64_t lddc_b; const int32_t *c_row_idx;
@@ -34,6 +45,10 @@ struct WgradDev {
   const int32_t *rd_off; int32_t rd_G, rd_chunk;
   float *rd_dW; int32_t rd_beta;
   const float *rd_bws; int64_t rd_b4; float *rd_db; int32_t rd_beta_db;
+  // rd_n > 1: the previous call was a batched launch (m3_wgrad_multi) - rd_n dense reductions of rd_splits slabs each, their
+  // blocks one problem after the other (rd_tab[j].first); the table replaces rd_ws .. rd_beta_db above
+  int32_t rd_n;
+  WgradRdProb rd_tab0, rd_tab1, rd_tab2, rd_tab3, rd_tab4, rd_tab5, rd_tab6, rd_tab7;
   // direct mode (splits == 1, no balanced units: every (group, tile) belongs to exactly ONE workgroup): the result tiles are
   // added into dW [G][N][K] (the column sums into db [G][N]) by the kernel itself - no slabs, no reduction
   float *direct_dW; float *direct_db; int32_t direct_beta, direct_beta_db;
@@ -132,6 +147,20 @@ __device__ __forceinline__ int wgrad_lpt_group(const int32_t *off, int G, int u,
   const unsigned long long m = __ballot(lane < G && rank == want);
   return __ffsll((long long)m) - 1;
 }
+
+// A batched launch (m3_wgrad_multi, wgrad_multi.hip): up to WG_MULTI dense problems over the same M rows, every one cut into
+// the same d.splits row parts.  `d` carries what the problems share (M, splits, the reduction riding in front); a workgroup
+// copies its problem's operands, shape and slabs from the table into it.
+struct WgradProb {
+  const char *dC; int64_t lddc_b; const char *A; int64_t lda_b;
+  float *ws; float *bias_ws;       // this problem's slabs [splits][N][K] and (or null) [splits][N]
+  int32_t N, K, tiles_k;
+  int32_t first;                   // the first tile of this problem among the launch's tiles; INT32_MAX in the unused entries
+};
+struct WgradMultiDev {
+  WgradDev d;
+  WgradProb tab0, tab1, tab2, tab3, tab4, tab5, tab6, tab7;
+};
 
 typedef __fp16 fp16x4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
 
@@ -238,7 +267,28 @@ __device__ __forceinline__ bool wgrad_ride_along(const WgradDev &p, int tid, int
     const int rid = blockIdx.x + (int)gridDim.x * (blockIdx.y + (int)gridDim.y * bz);
     if (rid < p.rd_blocks) {
       const int g = rid / p.rd_nbx, bx = rid - g * p.rd_nbx;
-      if (p.rd_chunk)
+      if (p.rd_n > 1) {
+        const float *ws = p.rd_tab0.ws, *bws = p.rd_tab0.bws;
+        float *dW = p.rd_tab0.dW, *db = p.rd_tab0.db;
+        int64_t e4 = p.rd_tab0.e4;
+        int b4 = p.rd_tab0.b4, nbw = p.rd_tab0.nbw, first = p.rd_tab0.first, beta = p.rd_tab0.beta;
+        // every entry is read, then chosen by value: reads under the condition come out as a choice between ADDRESSES of
+        // table entries, and the table then stays in scratch, written there by every workgroup of every launch
+#define M3_RD_FROM(j)                                                                                                   \
+  {                                                                                                                     \
+    const float *ws_ = p.rd_tab##j.ws, *bws_ = p.rd_tab##j.bws;                                                         \
+    float *dW_ = p.rd_tab##j.dW, *db_ = p.rd_tab##j.db;                                                                 \
+    const int64_t e4_ = p.rd_tab##j.e4;                                                                                 \
+    const int b4_ = p.rd_tab##j.b4, nbw_ = p.rd_tab##j.nbw, first_ = p.rd_tab##j.first, beta_ = p.rd_tab##j.beta;       \
+    const bool h_ = rid >= first_;                                                                                      \
+    ws = h_ ? ws_ : ws; bws = h_ ? bws_ : bws; dW = h_ ? dW_ : dW; db = h_ ? db_ : db; e4 = h_ ? e4_ : e4;              \
+    b4 = h_ ? b4_ : b4; nbw = h_ ? nbw_ : nbw; first = h_ ? first_ : first; beta = h_ ? beta_ : beta;                   \
+  }
+        static_assert(WG_MULTI == 8, "one M3_RD_FROM per entry");
+        M3_RD_FROM(1) M3_RD_FROM(2) M3_RD_FROM(3) M3_RD_FROM(4) M3_RD_FROM(5) M3_RD_FROM(6) M3_RD_FROM(7)
+#undef M3_RD_FROM
+        wgrad_reduce_block(rid - first, tid, ws, p.rd_splits, e4, dW, beta & 1, nbw, bws, b4, db, beta >> 1, p.rd_cols);
+      } else if (p.rd_chunk)
         wgrad_reduce_grouped_block(bx, g, tid, p.rd_ws, p.rd_off, p.rd_G, p.rd_chunk, p.rd_e4, p.rd_dW, p.rd_beta, p.rd_nbw,
                                    p.rd_bws, p.rd_b4, p.rd_db, p.rd_beta_db);
       else
@@ -342,5 +392,6 @@ static inline int wgrad_launch_instance(int dtype, bool gc, bool ga, bool sc, di
 int launch_wgrad_staged(int dtype, bool gc, bool ga, bool sc, dim3 grid, const WgradDev &d, hipStream_t s);   // wgrad_staged.hip
 int launch_wgrad_dma(int dtype, bool gc, bool ga, bool sc, dim3 grid, const WgradDev &d, hipStream_t s);      // wgrad_dma.hip
 int launch_wgrad_big(int dtype, bool gc, bool ga, bool sc, dim3 grid, const WgradDev &d, hipStream_t s);
+int launch_wgrad_multi(int dtype, dim3 grid, const WgradMultiDev &d, hipStream_t s);                          // wgrad_multi.hip
 
 }  // namespace m3

@@ -52,8 +52,12 @@ __device__ __forceinline__ f32x4 read_tr_frag<float>(const char *base, int rb, i
   return f;
 }
 
-template <typename T, bool GC, bool GA, bool SC = false>
-__global__ __launch_bounds__(WG_THREADS, 2) void wgrad_tn_kernel(const WgradDev p) {
+// One workgroup's work once it knows what is its own: output tile `tile` of group g over the 32-row steps s_begin .. s_begin +
+// nst - 1 of the rows r0 .. r1 - 1, result to slab `slab_id` (or into dW: direct mode).  Shared by wgrad_tn_kernel and the
+// batched wgrad_multi_kernel (wgrad_multi.hip).
+template <typename T, bool GC, bool GA, bool SC>
+__device__ __forceinline__ void wgrad_tile_loop(const WgradDev &p, int tile, int g, int64_t slab_id, int64_t r0, int64_t r1,
+                                                int64_t s_begin, int nst) {
   typedef Mma<T> MM;
   typedef typename MM::frag frag;
   constexpr int ES = (int)sizeof(T);
@@ -73,37 +77,8 @@ __global__ __launch_bounds__(WG_THREADS, 2) void wgrad_tn_kernel(const WgradDev 
   const int li = lane & 15, lg = lane >> 4;
   const int wr = wave >> 1, wc = wave & 1;
 
-  // XCD-aware order: all tiles of one (group, split) read the SAME rows of dC and A (each byte is
-  // needed by tiles_k resp. tiles_n workgroups), so they are given consecutive logical ids, which the
-  // remap places on one XCD: the re-reads hit that XCD's L2 instead of the fabric.
-  const int tiles = gridDim.x;
-  int bz, gz;
-  if (wgrad_ride_along(p, tid, bz, gz)) return;
-  const int lin = blockIdx.x + tiles * (blockIdx.y + gridDim.y * bz);
-  int tile, gs, g, sp, nst;
-  int64_t r0, r1, s_begin;
-  if (p.chunk_rows) {                          // gs = work unit; its slab is ws[gs]
-    if (!wgrad_unit(p.group_offsets, p.G, p.chunk_rows, lin, tiles, lane, tile, gs, g, r0, r1)) return;
-    sp = gs; s_begin = 0;
-    nst = (int)((r1 - r0 + ROWS - 1) / ROWS);
-  } else {
-    const int log_id = xcd_remap(lin, tiles * gridDim.y * gz);
-    tile = log_id % tiles; gs = log_id / tiles;
-    g = gs % (int)gridDim.y; sp = gs / (int)gridDim.y;
-    if (p.group_offsets && p.lpt) g = wgrad_lpt_group(p.group_offsets, p.G, g, lane);
-    if (p.group_offsets) { r0 = p.group_offsets[g]; r1 = p.group_offsets[g + 1]; }
-    else { r0 = 0; r1 = p.M; }
-    const int64_t nsteps_all = (r1 - r0 + ROWS - 1) / ROWS;
-    const int64_t per = (nsteps_all + p.splits - 1) / p.splits;
-    s_begin = (int64_t)sp * per;
-    int64_t s_end = s_begin + per;
-    if (s_end > nsteps_all) s_end = nsteps_all;
-    nst = (int)(s_end > s_begin ? s_end - s_begin : 0);
-  }
   const int tn = tile / p.tiles_k, tk = tile - tn * p.tiles_k;
   const int n0 = tn * WG_T, k0 = tk * WG_T;
-  // slab / bias slab of this workgroup
-  const int64_t slab_id = p.chunk_rows ? (int64_t)sp : (int64_t)sp * p.G + g;
 
   f32x4 acc[4][4];   // [ki][ni]: MFMA rows = k, cols = n
 #pragma unroll
@@ -249,6 +224,44 @@ __global__ __launch_bounds__(WG_THREADS, 2) void wgrad_tn_kernel(const WgradDev 
     }
   }
   wgrad_store_tile(p, acc, slab_id, g, n0, k0, wr, wc, li, lg);
+}
+
+template <typename T, bool GC, bool GA, bool SC = false>
+__global__ __launch_bounds__(WG_THREADS, 2) void wgrad_tn_kernel(const WgradDev p) {
+  constexpr int ROWS = WgLds<T>::ROWS;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+
+  // XCD-aware order: all tiles of one (group, split) read the SAME rows of dC and A (each byte is
+  // needed by tiles_k resp. tiles_n workgroups), so they are given consecutive logical ids, which the
+  // remap places on one XCD: the re-reads hit that XCD's L2 instead of the fabric.
+  const int tiles = gridDim.x;
+  int bz, gz;
+  if (wgrad_ride_along(p, tid, bz, gz)) return;
+  const int lin = blockIdx.x + tiles * (blockIdx.y + gridDim.y * bz);
+  int tile, gs, g, sp, nst;
+  int64_t r0, r1, s_begin;
+  if (p.chunk_rows) {                          // gs = work unit; its slab is ws[gs]
+    if (!wgrad_unit(p.group_offsets, p.G, p.chunk_rows, lin, tiles, lane, tile, gs, g, r0, r1)) return;
+    sp = gs; s_begin = 0;
+    nst = (int)((r1 - r0 + ROWS - 1) / ROWS);
+  } else {
+    const int log_id = xcd_remap(lin, tiles * gridDim.y * gz);
+    tile = log_id % tiles; gs = log_id / tiles;
+    g = gs % (int)gridDim.y; sp = gs / (int)gridDim.y;
+    if (p.group_offsets && p.lpt) g = wgrad_lpt_group(p.group_offsets, p.G, g, lane);
+    if (p.group_offsets) { r0 = p.group_offsets[g]; r1 = p.group_offsets[g + 1]; }
+    else { r0 = 0; r1 = p.M; }
+    const int64_t nsteps_all = (r1 - r0 + ROWS - 1) / ROWS;
+    const int64_t per = (nsteps_all + p.splits - 1) / p.splits;
+    s_begin = (int64_t)sp * per;
+    int64_t s_end = s_begin + per;
+    if (s_end > nsteps_all) s_end = nsteps_all;
+    nst = (int)(s_end > s_begin ? s_end - s_begin : 0);
+  }
+  // slab / bias slab of this workgroup
+  const int64_t slab_id = p.chunk_rows ? (int64_t)sp : (int64_t)sp * p.G + g;
+  wgrad_tile_loop<T, GC, GA, SC>(p, tile, g, slab_id, r0, r1, s_begin, nst);
 }
 
 // the instances: every dtype with every pair of gathers; a per-row factor only on gathered dC rows

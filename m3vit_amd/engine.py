@@ -21,6 +21,7 @@ torch is used for buffer ownership and for the O(E) cv-loss arithmetic only.
 """
 from __future__ import annotations
 
+import os
 from typing import Dict, Optional
 
 import torch
@@ -225,6 +226,10 @@ class BackboneEngine(ExpertParallelMixin):
         self.s_dxa = self._e(T, D, dtype=f32)
         self.s_dxb = self._e(T, D, dtype=f32)
         self.s_dx_t = self._e(T, D)
+        self._plan_wgrad_batch()
+        # batched weight gradients: the copy the norm2 backward emits (proj's dC) gets a buffer of its own, because the block-entry
+        # copy in s_dx_t (fc2's dC) is read again by the block's one weight-gradient launch
+        self.s_dx_tb = self._e(T, D) if self.wgrad_batched else None
         self.s_dpre = self._e(max(T * self.Hd, R * self.Hm))
         self.s_dh = self._e(T, D)
         self.s_dh32 = self._e(T, D, dtype=f32)
@@ -250,6 +255,11 @@ class BackboneEngine(ExpertParallelMixin):
         # one stream order with flush())
         self.wq = ops.WgradQueue(wg, self.dev) if self.wg_stream is None else None
         self.ws_wgrad = self._e(wg, dtype=f32) if self.wq is None else None
+        # the batched launches' slabs: two buffers of their own, used in turn (a batch's reductions are pending until the next
+        # weight-gradient launch of the pass; the queue's buffers stay as large as the largest single call needs)
+        wgm = max(ops.wgrad_multi_ws_elems(b, T, self.dt) for b in self._wgrad_batch_shapes().values()) if self.wgrad_batched else 0
+        self.ws_wgrad_multi = [self._e(wgm, dtype=f32) for _ in range(2)] if self.wgrad_batched else None
+        self._wgm_i = 0
         cs = max(int(ops.lib().m3_colsum_ws_elems(T, 3 * D, 1)), int(ops.lib().m3_colsum_ws_elems(T, self.Hd, 1)),
                  int(ops.lib().m3_colsum_ws_elems(R, max(self.Hm, D), self.E)))
         self.ws_colsum = self._e(cs, dtype=f32)
@@ -604,6 +614,46 @@ class BackboneEngine(ExpertParallelMixin):
             torch.cuda.current_stream().wait_stream(self.wg_stream)
             self._readers.clear()
 
+    def _wgrad_batch_shapes(self):
+        """(N, K, has bias) of the dense-row weight gradients of a dense / an MoE block, in the order the backward produces them"""
+        D, Hd = self.D, self.Hd
+        attn = [(D, D, True), (3 * D, D, True)]
+        return {"dense": [(D, Hd, True), (Hd, D, True)] + attn, "moe": attn}
+
+    def _plan_wgrad_batch(self):
+        """Batched weight gradients: the dense-row weight gradients of a block's backward - fc2, fc1, proj, qkv of a dense block,
+        proj, qkv of an MoE block - go out as ONE launch (ops.wgrad_multi) behind the block's attention backward instead of
+        one launch each where their dC appears; the experts' and the router's stay where they are.  M3_WGRAD_BATCH=0 / 1
+        forces the per-weight / the batched path (default: batched).  The per-weight path stays where the batch cannot
+        run: with a weight-gradient side stream (its launches are ordered by events per operand), under activation
+        checkpointing and expert parallelism (not wired), and where the library refuses the batch (fp32, the ViT-Base
+        widths: ops.wgrad_multi_plan).  self.wgrad_batched says which path runs, self.wgrad_batch_why why not."""
+        why = None
+        if os.environ.get("M3_WGRAD_BATCH", "1") == "0":
+            why = "M3_WGRAD_BATCH=0"
+        elif self.wg_stream is not None:
+            why = "weight-gradient side stream"
+        elif self.checkpoint:
+            why = "activation checkpointing"
+        elif self.ep_world > 1:
+            why = "expert parallelism"
+        elif not all(ops.wgrad_multi_plan(b, self.T, self.dt).allowed for b in self._wgrad_batch_shapes().values()):
+            why = "refused by m3_wgrad_multi_plan"
+        self.wgrad_batched, self.wgrad_batch_why = why is None, why
+        self.wgrad_multi_calls = 0
+
+    def _wgrad_or_batch(self, batch, dC, A, name, bias, reads):
+        """a dense-row weight gradient: launched now (batch is None), or put on the block's list for _wgrad_batch"""
+        if batch is None:
+            self._wgrad(dC, A, name, bias=bias, reads=reads)
+        else:
+            batch.append((dC, A, self.grads[name], self.grads[bias], 1))
+
+    def _wgrad_batch(self, batch):
+        ops.wgrad_multi(batch, self.T, ws=self.ws_wgrad_multi[self._wgm_i], queue=self.wq)
+        self._wgm_i ^= 1
+        self.wgrad_multi_calls += 1
+
     def _wgrad(self, dC, A, name, M=None, bias=None, reads=(), **kw):
         """weight grad (+ fused bias grad) accumulated into self.grads"""
         self._fork(reads, lambda: ops.wgrad_tn(dC, A, self.grads[name], M=M, beta=1, ws=self.ws_wgrad, queue=self.wq,
@@ -639,6 +689,10 @@ class BackboneEngine(ExpertParallelMixin):
             if self.checkpoint:                             # the shared activation buffers hold another block's values
                 self._block_forward(i, a["x_in"], None)
             sa, sm = (None, None) if a.get("ps") is None else a["ps"]
+            # batched weight gradients: the block's dense-row calls are collected and launched once, behind the attention
+            # backward; until then s_dx_t keeps fc2's dC, so the norm2 backward's copy (proj's dC) goes to s_dx_tb
+            batch = [] if self.wgrad_batched else None
+            dx_t1 = self.s_dx_tb if self.wgrad_batched else self.s_dx_t
             if not self.is_moe[i]:
                 if sm is not None:                          # DropPath: the gradient entering the branch is scale * d x
                     self._before_write("dx_t")
@@ -647,10 +701,10 @@ class BackboneEngine(ExpertParallelMixin):
                     self._before_write("dx_t")
                     ops.cast_f32(dx, self.s_dx_t)
                 dpre = self.s_dpre[: T * self.Hd].view(T, self.Hd)
-                self._wgrad(self.s_dx_t, a["u"], b + "mlp.fc2.weight", bias=b + "mlp.fc2.bias", reads=("dx_t",))
+                self._wgrad_or_batch(batch, self.s_dx_t, a["u"], b + "mlp.fc2.weight", b + "mlp.fc2.bias", ("dx_t",))
                 self._before_write("dpre")
                 ops.gemm_nt(self.s_dx_t, self.wt[b + "mlp.fc2"], dpre, gelu_grad_pre=a["pre"])
-                self._wgrad(dpre, a["h2"], b + "mlp.fc1.weight", bias=b + "mlp.fc1.bias", reads=("dpre",))
+                self._wgrad_or_batch(batch, dpre, a["h2"], b + "mlp.fc1.weight", b + "mlp.fc1.bias", ("dpre",))
                 ops.gemm_nt(dpre, self.wt[b + "mlp.fc1"], self.s_dh)
                 dh2 = self.s_dh
             else:
@@ -716,16 +770,18 @@ class BackboneEngine(ExpertParallelMixin):
             self._before_write("dx_t")
             ops.layernorm_bwd(dh2, a["x1"], a["mean2"], a["rstd2"], p[b + "norm2.weight"], dx, other, None, None,
                               ws=self.ws_ln[2 * i + 1],
-                              dx_act=self.s_dx_t if sa is None else None)     # also emits the activation-dtype copy
+                              dx_act=dx_t1 if sa is None else None)           # also emits the activation-dtype copy
             dx, other = other, dx                                        # dx = d x1
             if sa is not None:
-                ops.scale_rows_cast(dx, sa, self.N, self.s_dx_t)         # DropPath of the attention branch
-            self._wgrad(self.s_dx_t, a["o"], b + "attn.proj.weight", bias=b + "attn.proj.bias", reads=("dx_t",))
-            ops.gemm_nt(self.s_dx_t, self.wt[b + "attn.proj"], self.s_do)
+                ops.scale_rows_cast(dx, sa, self.N, dx_t1)               # DropPath of the attention branch
+            self._wgrad_or_batch(batch, dx_t1, a["o"], b + "attn.proj.weight", b + "attn.proj.bias", ("dx_t",))
+            ops.gemm_nt(dx_t1, self.wt[b + "attn.proj"], self.s_do)
             self._before_write("dqkv")
             ops.attention_bwd(a["qkv"], a["o"], self.s_do, a["lse"], B, self.N, self.heads, self.dh, self.s_dqkv,
                               dq_ws=self.ws_dq)
-            self._wgrad(self.s_dqkv, a["h1"], b + "attn.qkv.weight", bias=b + "attn.qkv.bias", reads=("dqkv",))
+            self._wgrad_or_batch(batch, self.s_dqkv, a["h1"], b + "attn.qkv.weight", b + "attn.qkv.bias", ("dqkv",))
+            if batch is not None:                                        # before the norm1 backward overwrites s_dx_t
+                self._wgrad_batch(batch)
             ops.gemm_nt(self.s_dqkv, self.wt[b + "attn.qkv"], self.s_dh)
             # does the block below consume the activation-dtype copy of d x directly?  (a dense block without DropPath: fc2's
             # backward GEMMs; an MoE block with local experts: FC2's backward GEMMs, which apply the gate score themselves)

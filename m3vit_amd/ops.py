@@ -16,7 +16,8 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import M3_ACT_GELU, M3_ACT_NONE, M3_BF16, M3_F16, M3_F32, GemmArgs, WgradArgs, WgradPlan, WgradReduceDesc, WgradShape, check, lib
+from ._lib import (M3_ACT_GELU, M3_ACT_NONE, M3_BF16, M3_F16, M3_F32, GemmArgs, WgradArgs, WgradMultiArgs, WgradMultiPlan,
+                   WgradMultiShape, WgradPlan, WgradReduceDesc, WgradShape, check, lib)
 
 _DT = {torch.float32: M3_F32, torch.float16: M3_F16, torch.bfloat16: M3_BF16}      # bf16: every entry point
 
@@ -417,7 +418,7 @@ class WgradQueue:
     def __init__(self, ws_elems: int, device):
         self.ws = [torch.empty(ws_elems, dtype=torch.float32, device=device) for _ in range(2)]
         self.i = 0
-        self.pending = None          # (WgradReduceDesc, tensors it points at)
+        self.pending = None          # (ctypes array of WgradReduceDesc - one, or those of a wgrad_multi call -, tensors they point at)
 
     def reset(self):
         """drop a pending reduction without running it (step boundaries: see BackboneEngine.zero_grad)"""
@@ -427,10 +428,23 @@ class WgradQueue:
     def flush(self):
         if self.pending is None:
             return
-        d, _keep = self.pending
+        descs, _keep = self.pending
         self.pending = None
-        if d.elems:
-            _wgrad_reduce(d)
+        if len(descs) > 1:
+            check(lib().m3_wgrad_reduce_multi(descs, len(descs), _stream()), "m3_wgrad_reduce_multi")
+        elif descs[0].elems:
+            _wgrad_reduce(descs[0])
+
+    def take_prev(self, a, writes=()):
+        """the pending reduction into a.prev / a.n_prev of the next call's arguments; one that writes a tensor the call
+        itself writes (data pointers in `writes`) cannot ride in front of it and runs now"""
+        if self.pending is None:
+            return
+        if any(d.dW in writes or (d.db is not None and d.db in writes) for d in self.pending[0]):
+            self.flush()
+            return
+        a.prev = ctypes.cast(self.pending[0], ctypes.POINTER(WgradReduceDesc))
+        a.n_prev = len(self.pending[0])
 
 
 def wgrad_launch_plan(M, N, K, G, dtype, *, grouped, bias=True, splits=0, direct_ok=False) -> WgradPlan:
@@ -503,14 +517,10 @@ def wgrad_tn(dC, A, dW, *, M=None, beta=0, splits=None, ws=None, c_row_idx=None,
     a.dtype = dt_code(dC.dtype)
     if db is not None:
         _req(db, torch.float32, "db")
-    prev = queue.pending if queue is not None else None
     if p.direct:
         a.direct_dW = dW.data_ptr(); a.direct_beta = 1 if beta else 0
         a.direct_db = db.data_ptr() if db is not None else None
         a.direct_beta_db = 1 if bdb else 0
-        if prev is not None and prev[0].dW == dW.data_ptr():       # the previous reduction writes the tensor this launch
-            queue.flush()                                          # read-add-writes: it cannot ride in front
-            prev = None
     else:
         # the reduction of this call's slabs; both slab kinds in one launch where db and the bias slabs are 16-byte aligned
         bias_ws = ws[p.units * N * K:] if db is not None else None
@@ -519,7 +529,8 @@ def wgrad_tn(dC, A, dW, *, M=None, beta=0, splits=None, ws=None, c_row_idx=None,
         assert db is None or fuse or queue is None, "queued wgrad: db and the bias slabs must be 16-byte aligned"
         assert db is None or fuse or not p.chunk_rows, "balanced grouped wgrad: db and the bias slabs must be 16-byte aligned"
         per = 1 if p.chunk_rows else G                              # balanced: elements per group, else of all groups
-        d = WgradReduceDesc()
+        descs = (WgradReduceDesc * 1)()
+        d = descs[0]
         d.ws = ws.data_ptr(); d.splits = p.splits; d.elems = per * N * K
         d.group_offsets = a.group_offsets if p.chunk_rows else None
         d.G = G; d.chunk_rows = p.chunk_rows
@@ -528,20 +539,87 @@ def wgrad_tn(dC, A, dW, *, M=None, beta=0, splits=None, ws=None, c_row_idx=None,
         d.bias_elems = per * N if fuse else 0
         d.db = db.data_ptr() if fuse else None
         d.beta_db = bdb
-    if prev is not None:                                           # the previous call's reduction rides in front
-        a.prev = ctypes.pointer(prev[0])
+    if queue is not None:                                          # the previous call's reduction rides in front; in direct mode
+        queue.take_prev(a, (a.direct_dW, a.direct_db) if p.direct else ())    # not one into the tensor this launch read-add-writes
     check(lib().m3_wgrad_tn(byref(a), _stream()), "m3_wgrad_tn")
     if p.direct:                                                   # nothing to reduce (and the queue's slab buffer was not used)
         if queue is not None:
             queue.pending = None
     elif queue is not None:
-        queue.pending = (d, (ws, dW, db, group_offsets))
+        queue.pending = (descs, (ws, dW, db, group_offsets))
         queue.i ^= 1
     else:
         _wgrad_reduce(d)
         if db is not None and not fuse:
             check(lib().m3_wgrad_bias_reduce(_p(bias_ws), p.splits, G * N, _p(db), bdb, _stream()), "m3_wgrad_bias_reduce")
     return dW
+
+
+def _wgrad_multi_shape(problems, M, dtype, parts):
+    s = WgradMultiShape()
+    s.M = M; s.dtype = dt_code(dtype); s.n = len(problems); s.parts = parts
+    for j, (N, K, bias) in enumerate(problems):
+        s.N[j] = N; s.K[j] = K; s.bias[j] = 1 if bias else 0
+    return s
+
+
+def wgrad_multi_plan(shapes, M, dtype, parts=0) -> WgradMultiPlan:
+    """How m3_wgrad_multi runs the batch of dense weight gradients `shapes` = [(N, K, has bias), ..] over M rows
+    (m3_wgrad_multi_plan in include/m3vit_hip.h): .allowed (0: keep a call per weight), .parts, .tiles, .workgroups,
+    .ws_elems fp32 elements of slab workspace.  parts = 0: the library's rule."""
+    assert 1 <= len(shapes) <= _lib.WGRAD_MULTI_MAX, f"1 .. {_lib.WGRAD_MULTI_MAX} problems"
+    p = WgradMultiPlan()
+    check(lib().m3_wgrad_multi_plan(byref(_wgrad_multi_shape(shapes, M, dtype, parts)), byref(p)), "m3_wgrad_multi_plan")
+    return p
+
+
+def wgrad_multi_ws_elems(shapes, M, dtype, parts=0) -> int:
+    """fp32 elements of workspace wgrad_multi needs for this batch"""
+    return wgrad_multi_plan(shapes, M, dtype, parts).ws_elems
+
+
+def wgrad_multi(problems, M, *, parts=0, ws=None, queue: Optional[WgradQueue] = None):
+    """dW_j (+)= dC_j^T A_j, db_j (+)= column sums of dC_j for every problem (dC, A, dW, db or None, beta[, beta_db]) in ONE
+    launch (m3_wgrad_multi): plain rows 0 .. M-1 of 16-bit operands, shapes wgrad_multi_plan allows.  queue: the slab
+    reductions are left pending in it and the queue's previous reduction runs in front of this launch; else they run
+    as one launch behind it.  With a queue, ws (optional) is the caller's slab buffer in place of the queue's next one: it
+    must stay untouched until the pending reduction has run, and must not be the buffer of the call before."""
+    n = len(problems)
+    assert 1 <= n <= _lib.WGRAD_MULTI_MAX, f"1 .. {_lib.WGRAD_MULTI_MAX} problems"
+    a = WgradMultiArgs()
+    dt = problems[0][0].dtype
+    shapes = []
+    for j, pr in enumerate(problems):
+        dC, A, dW, db, beta = pr[:5]
+        _req(dC, dt, "dC"); _req(A, dt, "A"); _req(dW, torch.float32, "dW")
+        N, K = dW.shape
+        assert dC.shape[0] >= M and A.shape[0] >= M and dC.shape[1] == N and A.shape[1] == K, "wgrad_multi: operand shapes"
+        q = a.prob[j]
+        q.dC = dC.data_ptr(); q.lddc = dC.stride(0); q.A = A.data_ptr(); q.lda = A.stride(0); q.N = N; q.K = K
+        q.dW = dW.data_ptr(); q.beta = 1 if beta else 0
+        if db is not None:
+            _req(db, torch.float32, "db", numel=N)
+            q.db = db.data_ptr(); q.beta_db = 1 if (beta if len(pr) < 6 else pr[5]) else 0
+        shapes.append((N, K, db is not None))
+    p = wgrad_multi_plan(shapes, M, dt, parts)
+    own_ws = ws is not None
+    if queue is not None:
+        ws = ws if own_ws else queue.ws[queue.i]
+        assert ws.numel() >= p.ws_elems, "wgrad_multi: slab workspace too small for this batch"
+    elif ws is None or ws.numel() < p.ws_elems:
+        ws = torch.empty(max(p.ws_elems, 4), dtype=torch.float32, device=problems[0][2].device)
+    a.M = M; a.dtype = dt_code(dt); a.n = n; a.parts = p.parts; a.ws = ws.data_ptr()
+    descs = (WgradReduceDesc * n)()
+    a.reduce_out = ctypes.cast(descs, ctypes.POINTER(WgradReduceDesc))
+    if queue is not None:
+        queue.take_prev(a, [t.data_ptr() for pr in problems for t in (pr[2], pr[3]) if t is not None])
+    check(lib().m3_wgrad_multi(byref(a), _stream()), "m3_wgrad_multi")
+    if queue is not None:
+        queue.pending = (descs, (ws, problems))
+        if not own_ws:
+            queue.i ^= 1
+    else:
+        check(lib().m3_wgrad_reduce_multi(descs, n, _stream()), "m3_wgrad_reduce_multi")
 
 
 def wgrad_set_big(on: int):
