@@ -1,5 +1,5 @@
 // Long-contraction NT GEMM for gfx950: 256 x 256 output tiles, eight waves, operands through a two-slot LDS ring filled by
-// LDS-DMA that stays in flight across barriers.  Same contract as gemm_nt_dma_kernel (gemm.hip): C[m,n] = epi(sum_k
+// LDS-DMA that stays in flight across barriers.  Same contract as gemm_nt_dma_kernel (gemm_dma.hip): C[m,n] = epi(sum_k
 // A[arow(m),k] * B[g][n,k]), grouped over experts, row gather on the A load, row scatter on the C store, the four
 // epilogue kinds.  It takes the launches whose contraction is long enough to amortise a 256 x 256 tile's prologue and
 // store phase: the ViT-Base shapes (K = 768 / 3072: expert FC1 / FC2 of BASELINE configs[3] / configs[4], reference call
@@ -33,7 +33,7 @@
 
 namespace m3 {
 
-constexpr int XB = 256;                  // tile edge
+constexpr int XB = BIG_B;                // tile edge
 constexpr int XT = 512;                  // threads
 constexpr int XH = 16384;                // one half-tile image: 128 rows x 128 B
 constexpr int XSLOT = 4 * XH;            // [A-m0 | B-n0 | B-n1 | A-m1]
@@ -82,11 +82,8 @@ __global__ __launch_bounds__(XT, 2) void gemm_nt_big_kernel(const GemmDev p) {
   tile_of(t, p.n_tiles, p.m_band, nwg / p.n_tiles, mt, nt);
   if (p.group_offsets) {
     g = __popcll(__ballot(incl <= mt));
-    int t0 = g ? __shfl(incl, g - 1, 64) : 0;
-    g = __builtin_amdgcn_readfirstlane(g);
-    t0 = __builtin_amdgcn_readfirstlane(t0);
-    m_begin = (int64_t)__builtin_amdgcn_readfirstlane(p.group_offsets[g]) + (int64_t)(mt - t0) * XB;
-    m_end = __builtin_amdgcn_readfirstlane(p.group_offsets[g + 1]);
+    const TileOwner ow = grouped_tile_rows<XB>(p.group_offsets, g, g ? __shfl(incl, g - 1, 64) : 0, mt);
+    g = ow.g; m_begin = ow.m_begin; m_end = ow.m_end;
   } else {
     m_begin = (int64_t)mt * XB;
     m_end = p.M;
@@ -319,36 +316,10 @@ __global__ __launch_bounds__(XT, 2) void gemm_nt_big_kernel(const GemmDev p) {
           const int lrow = ps * 16 + r16;
           const int64_t m = m_begin + h * 128 + lrow;
           if (m >= m_end) break;
-          const int64_t crow = p.c_row_idx ? (int64_t)p.c_row_idx[m] : m;
           const int sw = lrow & 31;
-          f32x4 v0 = *(const f32x4 *)(smem + lrow * 1024 + (((2 * cg) ^ sw) << 4));
-          f32x4 v1 = *(const f32x4 *)(smem + lrow * 1024 + (((2 * cg + 1) ^ sw) << 4));
-          v0 += bb0; v1 += bb1;
-          if (p.pre_out) Vec8<T>::store((T *)p.pre_out + crow * p.ld_pre + n, v0, v1);
-          if (p.act == M3_ACT_GELU) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { v0[j] = gelu_f(v0[j]); v1[j] = gelu_f(v1[j]); }
-          }
-          if (p.gpre) {
-            f32x4 p0, p1;
-            Vec8<T>::load((const T *)p.gpre + crow * p.ld_gpre + n, p0, p1);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { v0[j] *= gelu_grad_f(p0[j]); v1[j] *= gelu_grad_f(p1[j]); }
-          }
-          if (p.row_scale) {
-            const float sc = s_rs[h * 128 + lrow];
-            v0 *= sc; v1 *= sc;
-          }
-          if (p.residual) {
-            v0 += *(const f32x4 *)(p.residual + crow * p.ld_res + n);
-            v1 += *(const f32x4 *)(p.residual + crow * p.ld_res + n + 4);
-          }
-          if (p.c_f32) {
-            *(f32x4 *)((float *)p.C + crow * p.ldc + n) = v0;
-            *(f32x4 *)((float *)p.C + crow * p.ldc + n + 4) = v1;
-          } else {
-            Vec8<T>::store((T *)p.C + crow * p.ldc + n, v0, v1);
-          }
+          const f32x4 v0 = *(const f32x4 *)(smem + lrow * 1024 + (((2 * cg) ^ sw) << 4));
+          const f32x4 v1 = *(const f32x4 *)(smem + lrow * 1024 + (((2 * cg + 1) ^ sw) << 4));
+          epilogue_row_any<T>(p, m, n, v0 + bb0, v1 + bb1, [&](int64_t) { return s_rs[h * 128 + lrow]; });
         }
       }
     }
@@ -376,32 +347,25 @@ bool gemm_big_eligible(const GemmDev &d, int es, bool force) {
   return mt * ntl >= 96;
 }
 
-int launch_gemm_big(const GemmDev &d0, int dtype, int epi, hipStream_t s) {
-  GemmDev d = d0;
-  d.n_tiles = (d.N + XB - 1) / XB;
-  d.m_band = 1;             // row-tile major: a 256-row tile's A rows at K >= 2048 are 1 MB and more - four of them do not sit in an L2 (counters: banded +13 % fetch)
-  const int64_t mt = (d.M + XB - 1) / XB + (d.group_offsets ? d.G : 0);
-  static bool attr_done = false;
-  if (!attr_done) {
-#define X_ATTR(TT, E) (void)hipFuncSetAttribute((const void *)gemm_nt_big_kernel<TT, E>, hipFuncAttributeMaxDynamicSharedMemorySize, XLDS)
-#define X_ATTR_ALL(TT) X_ATTR(TT, DMA_EPI_ANY); X_ATTR(TT, DMA_EPI_GPRE); X_ATTR(TT, DMA_EPI_RES); X_ATTR(TT, DMA_EPI_PLAIN); X_ATTR(TT, DMA_EPI_GELU)
-    X_ATTR_ALL(half_t); X_ATTR_ALL(bf16_t);
-#undef X_ATTR_ALL
-#undef X_ATTR
-    attr_done = true;
-  }
-  const dim3 grid((unsigned)(mt * d.n_tiles)), block(XT);
-#define X_GO(TT)                                                                                                     \
-  do {                                                                                                               \
-    if (epi == DMA_EPI_GPRE) hipLaunchKernelGGL((gemm_nt_big_kernel<TT, DMA_EPI_GPRE>), grid, block, XLDS, s, d);    \
-    else if (epi == DMA_EPI_RES) hipLaunchKernelGGL((gemm_nt_big_kernel<TT, DMA_EPI_RES>), grid, block, XLDS, s, d);  \
-    else if (epi == DMA_EPI_PLAIN) hipLaunchKernelGGL((gemm_nt_big_kernel<TT, DMA_EPI_PLAIN>), grid, block, XLDS, s, d); \
-    else if (epi == DMA_EPI_GELU) hipLaunchKernelGGL((gemm_nt_big_kernel<TT, DMA_EPI_GELU>), grid, block, XLDS, s, d); \
-    else hipLaunchKernelGGL((gemm_nt_big_kernel<TT, DMA_EPI_ANY>), grid, block, XLDS, s, d);                         \
-  } while (0)
-  if (dtype == M3_F16) X_GO(half_t);
-  else X_GO(bf16_t);
-#undef X_GO
+int launch_gemm_big(const GemmDev &d, int dtype, int epi, hipStream_t s) {
+  static const bool attr_done = [] {
+    for (int e : {DMA_EPI_ANY, DMA_EPI_GPRE, DMA_EPI_RES, DMA_EPI_PLAIN, DMA_EPI_GELU})
+      with_epi(e, [](auto k) {
+        constexpr int E = decltype(k)::value;
+        (void)hipFuncSetAttribute((const void *)gemm_nt_big_kernel<half_t, E>, hipFuncAttributeMaxDynamicSharedMemorySize, XLDS);
+        (void)hipFuncSetAttribute((const void *)gemm_nt_big_kernel<bf16_t, E>, hipFuncAttributeMaxDynamicSharedMemorySize, XLDS);
+      });
+    return true;
+  }();
+  (void)attr_done;
+  const dim3 grid((unsigned)((int64_t)d.m_tiles_max * d.n_tiles)), block(XT);
+  auto go = [&](auto t) {
+    with_epi(epi, [&](auto e) {
+      hipLaunchKernelGGL((gemm_nt_big_kernel<decltype(t), decltype(e)::value>), grid, block, XLDS, s, d);
+    });
+  };
+  if (dtype == M3_F16) go(half_t());
+  else go(bf16_t());
   return check_launch("m3_gemm_nt");
 }
 

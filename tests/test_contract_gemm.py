@@ -74,6 +74,8 @@ PATHS = {
     "f16_staged_n132": (F16, 333, 132, 192, 8, 132, None),
     "bf16_staged_ldc+4": (BF16, 333, 384, 192, 8, 388, None),
     "f16_staged_ktail": (F16, 333, 256, 200, 0, 256, None),
+    "f32_staged_ktail": (F32, 333, 256, 72, 0, 256, None),       # K * 4 B = two whole 128-byte slices + a 32-byte tail
+    "bf16_staged_ktail": (BF16, 333, 256, 200, 0, 256, None),
     "f16_dma_band1_ldc+8": (F16, 1000, 384, 384, 8, 392, None),
     "bf16_dma_band4": (BF16, 300, 1536, 768, 0, 1536, 0),
     "f16_big_k512": (F16, 300, 384, 512, 0, 384, 1),
