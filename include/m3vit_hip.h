@@ -551,6 +551,57 @@ int m3_assemble_tokens(const float *patch, const float *cls, const float *pos, i
 int m3_tokens_bwd(const float *dtok, int B, int np_, int D, void *dpatch, int dtype, float *dpos,
                   float *dcls, int beta, void *stream);
 
+/* ------------------------------------------------------------- optimizer tail
+ * What every trainer of the reference runs behind the backward (GradScaler.unscale_, clip_grad_norm_, scaler.step of
+ * torch.optim.AdamW / Adam / SGD with parameter groups: pretrain/engine/train_one_epoch.py:35-61,
+ * pretrain/optim/optimizer.py:6-46, utils/common_config.py:866-896) in three launches over all parameter tensors.
+ *
+ * descs_dev: a DEVICE array, one descriptor per parameter tensor (all fp32, n elements each): master p, gradient g (never
+ * written), first moment / momentum buffer m, second moment v (NULL for SGD).  One workgroup updates one chunk of
+ * M3_OPTIM_CHUNK elements: chunk_start = running sum of ceil(n / M3_OPTIM_CHUNK) over the preceding descriptors,
+ * total_chunks the full sum.  vec_ok = 1 when p, g, m and v are all 16-byte aligned (16-byte accesses), else 0 (scalar
+ * accesses: a gradient that is a view into a flat buffer may start at any element).
+ *
+ * hyper: DEVICE fp32 [n_groups][M3_OPTIM_HYPER] = lr, beta1 (SGD: momentum), beta2, eps, weight_decay, flags
+ * (M3_OPTIM_DECOUPLED: p *= 1 - lr * wd, AdamW; else wd * p is added to the gradient.  M3_OPTIM_NESTEROV), beta1_lo,
+ * beta2_lo where beta = (double) beta_hi + (double) beta_lo restores the host's double (the bias corrections are formed
+ * from it in double: 1 - beta2 carries 1e-5 of relative error when beta2 is first rounded to fp32).
+ *
+ * state: DEVICE, m3_optim_state_elems(n_groups) floats, zero before the first call and then owned by these calls:
+ *   [0] skip (int32)  [1] step (int32, counts the steps that were NOT skipped)  [2] total_norm  [3] clip_coef
+ *   [4] inv_scale  [5] inv_scale * clip_coef  [6..7] spare, then 8 derived doubles per group (8-byte aligned base).
+ *
+ * m3_optim_prepare: (a) when want_norm, partials[c] = fp32 sum of squares of chunk c's gradient elements and
+ * partials[total_chunks + c] = 1 if one of them is not finite (partials: 2 * total_chunks floats, no initialisation);
+ * (b) one workgroup adds the partials in a fixed order in double, total_norm = sqrt(sum) * inv_scale with
+ * inv_scale = 1 / *grad_scale (1 when NULL), skip = non-finite | (*found_inf_in != 0, when given),
+ * clip_coef = min(1, max_norm / (total_norm + 1e-6)) (1 when max_norm <= 0), step += !skip, and each group's coefficients
+ * for step t (Adam: lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t), formed and kept in double).
+ * m3_optim_step: p, m (and v) of every tensor updated in one pass from g * inv_scale * clip_coef; with skip set nothing
+ * is written.  kind: M3_OPTIM_ADAMW / M3_OPTIM_ADAM (exp_avg, exp_avg_sq as torch; the group's M3_OPTIM_DECOUPLED flag is
+ * what tells them apart) or M3_OPTIM_SGD (buf = momentum * buf + g, dampening 0, optional nesterov; a zero buffer gives
+ * torch's first step).  The Adam update of an element is evaluated in double: p, m and v are each rounded to fp32
+ * once.  `hyper` of m3_optim_step is accepted for symmetry and not read: the step takes its coefficients from `state`.
+ * Results are bit-identical from run to run. */
+#define M3_OPTIM_CHUNK 4096
+#define M3_OPTIM_HYPER 8
+#define M3_OPTIM_ADAMW 0
+#define M3_OPTIM_ADAM 1
+#define M3_OPTIM_SGD 2
+#define M3_OPTIM_DECOUPLED 1
+#define M3_OPTIM_NESTEROV 2
+typedef struct m3_optim_desc {
+  float *p; float *g; float *m; float *v;
+  int64_t n;
+  int32_t group, chunk_start, vec_ok;
+} m3_optim_desc;
+int m3_optim_state_elems(int n_groups);
+int m3_optim_prepare(const m3_optim_desc *descs_dev, int n_desc, int total_chunks, const float *hyper, int n_groups,
+                     int kind, const float *grad_scale, const float *found_inf_in, float max_norm, int want_norm,
+                     float *partials, float *state, void *stream);
+int m3_optim_step(const m3_optim_desc *descs_dev, int n_desc, int total_chunks, const float *hyper, const float *state,
+                  int kind, void *stream);
+
 /* -------------------------------------------------- decoder-head element-wise stage ("custom later")
  * ReLU (optional) + bilinear x2 up-sampling with align_corners = False in one pass, channels-last: the element-wise half of a
  * stage of models/heads/vit_up_head.py:181-214 (F.relu(syncbn(conv(x))) then F.interpolate(.., size = 2x, mode='bilinear')).

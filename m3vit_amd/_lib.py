@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("M3VIT_LIB") or os.path.join(_HERE, "libm3vit_hip.so")
 
 M3_F32, M3_F16, M3_BF16 = 0, 1, 2
 M3_ACT_NONE, M3_ACT_GELU = 0, 1
+M3_OPTIM_ADAMW, M3_OPTIM_ADAM, M3_OPTIM_SGD = 0, 1, 2
+M3_OPTIM_CHUNK, M3_OPTIM_HYPER, M3_OPTIM_DECOUPLED, M3_OPTIM_NESTEROV = 4096, 8, 1, 2
 
 
 class M3Error(RuntimeError):
@@ -107,6 +109,11 @@ class CastDesc(Structure):
                 ("cols", c_int32), ("tile_start", c_int32)]
 
 
+class OptimDesc(Structure):
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_int64),
+                ("group", c_int32), ("chunk_start", c_int32), ("vec_ok", c_int32)]
+
+
 class GateFwdArgs(Structure):
     _fields_ = [
         ("x", c_void_p), ("x_dtype", c_int32), ("T", c_int64), ("D", c_int32), ("ldx", c_int64),
@@ -190,6 +197,9 @@ SIGNATURES = {
     "m3_cast_matrix": (c_int, [_V, _I, _I, _I, _I, _V, _I, _V]),
     "m3_cast_batch": (c_int, [_V, _I, _I, _I, _V]),
     "m3_add_f32": (c_int, [_V, _V, _L, _V]),
+    "m3_optim_state_elems": (c_int, [_I]),
+    "m3_optim_prepare": (c_int, [_V, _I, _I, _V, _I, _I, _V, _V, _F, _I, _V, _V, _V]),
+    "m3_optim_step": (c_int, [_V, _I, _I, _V, _V, _I, _V]),
     "m3_cast_f32": (c_int, [_V, _L, _V, _I, _V]),
     "m3_scale_rows_cast": (c_int, [_V, _L, _I, _V, _I, _V, _I, _V]),
     "m3_im2row": (c_int, [_V, _I, _I, _I, _I, _I, _V, _I, _V]),

@@ -876,6 +876,124 @@ def add_f32(dst, src):
     return dst
 
 
+# ------------------------------------------------------------------------ optimizer
+OPTIM_KINDS = {"adamw": _lib.M3_OPTIM_ADAMW, "adam": _lib.M3_OPTIM_ADAM, "sgd": _lib.M3_OPTIM_SGD}
+
+
+def optim_table(rows):
+    """host half of the descriptor table of m3_optim_prepare / m3_optim_step: rows = [(p_ptr, g_ptr, m_ptr, v_ptr or 0, n,
+    group)] -> (ctypes array of m3_optim_desc, total_chunks).  chunk_start is the running sum of ceil(n / 4096); vec_ok is
+    set when every pointer of the row is 16-byte aligned (the 16-byte path), else the row takes the scalar path."""
+    arr = (_lib.OptimDesc * len(rows))()
+    c0 = 0
+    for d, (pp, pg, pm, pv, n, group) in zip(arr, rows):
+        if n < 1:
+            raise _lib.M3Error("an optimizer descriptor needs at least one element")
+        d.p, d.g, d.m, d.v, d.n, d.group, d.chunk_start = pp, pg, pm, pv or None, n, group, c0
+        d.vec_ok = int(all(q % 16 == 0 for q in (pp, pg, pm, pv or 0)))
+        c0 += -(-n // _lib.M3_OPTIM_CHUNK)
+    if c0 >= 2 ** 31:
+        raise _lib.M3Error("too many optimizer chunks for one launch")
+    return arr, c0
+
+
+def optim_hyper_row(lr, beta1=0.0, beta2=0.0, eps=0.0, weight_decay=0.0, decoupled=False, nesterov=False):
+    """one row of the fp32 [groups][8] hyper-parameter table: lr, beta1 (SGD: momentum), beta2, eps, weight_decay, flags,
+    and the low halves of beta1 / beta2 (beta = fp32 hi + fp32 lo carries the Python double to the device)"""
+    import struct
+    f32 = lambda x: struct.unpack("f", struct.pack("f", x))[0]                 # noqa: E731
+    b1, b2 = float(beta1), float(beta2)
+    flags = (_lib.M3_OPTIM_DECOUPLED if decoupled else 0) | (_lib.M3_OPTIM_NESTEROV if nesterov else 0)
+    return (float(lr), f32(b1), f32(b2), float(eps), float(weight_decay), float(flags), b1 - f32(b1), b2 - f32(b2))
+
+
+class OptimPlan:
+    """Device-resident tables of the fused optimizer step (m3_optim_prepare, m3_optim_step), analogous to CastPlan: one
+    descriptor per parameter tensor, one hyper-parameter row per group, plus the norm partials and the `state` block
+    (skip flag, step counter, total_norm, clip_coef, inv_scale and the per-group coefficients) the two calls share.
+
+    entries: [(p, g, m, v or None, group)] fp32 contiguous GPU tensors of equal element counts (v None for SGD);
+    state: the state block of an earlier plan over the same groups (keeps the step counter), else a zeroed one is made."""
+
+    def __init__(self, entries, n_groups, kind, state=None):
+        if kind not in OPTIM_KINDS:
+            raise _lib.M3Error(f"unknown optimizer kind {kind!r}; one of {sorted(OPTIM_KINDS)}")
+        if not entries:
+            raise _lib.M3Error("OptimPlan needs at least one parameter tensor")
+        self.kind, self.n_groups = OPTIM_KINDS[kind], int(n_groups)
+        rows, self.keep = [], []
+        for p, g, m, v, group in entries:
+            n = _req(p, torch.float32, "parameter").numel()
+            _req(g, torch.float32, "gradient", n); _req(m, torch.float32, "first-moment / momentum state", n)
+            if (v is None) != (kind == "sgd"):
+                raise _lib.M3Error("the second-moment state is given for Adam / AdamW and only for them")
+            if v is not None:
+                _req(v, torch.float32, "second-moment state", n)
+            if not 0 <= group < self.n_groups:
+                raise _lib.M3Error(f"group {group} outside 0 .. {self.n_groups - 1}")
+            rows.append((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr() if v is not None else 0, n, group))
+            self.keep += [p, g, m, v]
+        dev = entries[0][0].device
+        arr, self.total = optim_table(rows)
+        self.n = len(rows)
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+        self.hyper = torch.zeros(self.n_groups, _lib.M3_OPTIM_HYPER, dtype=torch.float32, device=dev)
+        self.hyper_rows = None
+        self.partials = torch.empty(2 * self.total, dtype=torch.float32, device=dev)
+        elems = lib().m3_optim_state_elems(self.n_groups)
+        if state is not None:
+            _req(state, torch.float32, "state", elems)
+        self.state = state if state is not None else torch.zeros(elems, dtype=torch.float32, device=dev)
+
+    def set_hyper(self, rows):
+        """rows: one optim_hyper_row per group.  Copied to the device (one non-blocking copy from a pinned buffer) only when
+        a value differs from what the device table holds."""
+        rows = [tuple(r) for r in rows]
+        if rows == self.hyper_rows:
+            return
+        if len(rows) != self.n_groups or any(len(r) != _lib.M3_OPTIM_HYPER for r in rows):
+            raise _lib.M3Error(f"the hyper-parameter table is [{self.n_groups}][{_lib.M3_OPTIM_HYPER}]")
+        # a fresh pinned buffer per change (torch's host allocator keeps it alive until the copy has run): the previous
+        # copy may still be in flight and nothing here waits for the device
+        host = torch.tensor(rows, dtype=torch.float64).to(torch.float32).pin_memory()
+        self.hyper.copy_(host, non_blocking=True)
+        self.hyper_rows = rows
+
+    def prepare(self, grad_scale=None, found_inf=None, max_norm=0.0, want_norm=False):
+        """the norm / skip / coefficient half of a step, on the current stream.  grad_scale, found_inf: 1-element fp32 GPU
+        tensors or None (what torch.amp.GradScaler.step hands to an optimizer that supports AMP scaling)."""
+        if self.hyper_rows is None:
+            raise _lib.M3Error("OptimPlan.set_hyper() has not been called")
+        for t, name in ((grad_scale, "grad_scale"), (found_inf, "found_inf")):
+            if t is not None:
+                _req(t, torch.float32, name, 1)
+        want = bool(want_norm) or max_norm > 0
+        check(lib().m3_optim_prepare(_p(self.table), self.n, self.total, _p(self.hyper), self.n_groups, self.kind,
+                                     _p(grad_scale), _p(found_inf), float(max_norm), int(want), _p(self.partials),
+                                     _p(self.state), _stream()), "m3_optim_prepare")
+
+    def step(self):
+        check(lib().m3_optim_step(_p(self.table), self.n, self.total, _p(self.hyper), _p(self.state), self.kind, _stream()),
+              "m3_optim_step")
+
+    # views of the state block (device tensors; reading one is the caller's synchronisation)
+    @property
+    def skipped(self):
+        return self.state[0:1].view(torch.int32)[0]
+
+    @property
+    def step_count(self):
+        return self.state[1:2].view(torch.int32)[0]
+
+    @property
+    def total_norm(self):
+        return self.state[2]
+
+    @property
+    def clip_coef(self):
+        return self.state[3]
+
+
 def cast_f32(src, dst):
     _req(src, torch.float32, "src"); _act(dst, "dst", src.numel())
     check(lib().m3_cast_f32(_p(src), src.numel(), _p(dst), dt_code(dst.dtype), _stream()), "m3_cast_f32")
