@@ -613,6 +613,73 @@ int m3_relu_up2x_fwd(const void *x, int x_dtype, int64_t N, int H, int W, int C,
 int m3_relu_up2x_bwd(const void *dy, int dy_dtype, const void *x, int x_dtype, int64_t N, int H, int W, int C,
                      int relu, void *dx, void *stream);
 
+/* ------------------------------------------------------------- dense-prediction losses
+ * The criterion between the decoder heads and the backward: the four losses utils/common_config.py:780-807 (get_loss) can
+ * return - SoftMaxwithLoss (losses/loss_functions.py:16-33), BalancedCrossEntropyLoss (:36-84, size_average, no void_pixels),
+ * DepthLoss('l1') (:126-140) and NormalsLoss(normalize=True, size_average=True, norm = 1 | 2) (:143-197) - each as a forward
+ * (two launches: per-workgroup partials, then one workgroup that adds them in block order in double) and one backward launch.
+ * No atomics, nothing read back to the host, the same bits from run to run.
+ *
+ * pred: [B,C,H,W] values of `dtype` (M3_F32 / M3_F16 / M3_BF16) in one of two layouts: M3_LAYOUT_NCHW (contiguous) or
+ * M3_LAYOUT_NHWC (channels-last storage, what m3_relu_up2x_fwd writes).  dpred: the same dtype and layout.  Arithmetic is fp32.
+ * 16-byte accesses where pred / dpred / lse are 16-byte aligned and rows fill whole vectors (NCHW: H*W % 4 == 0; NHWC cross-
+ * entropy: C % 4 == 0; L1 / BCE: B*C*H*W % 4 == 0), scalar accesses otherwise; B*C*H*W < 2^31 - 2^20.
+ * label: cross-entropy: one class per pixel, [B*H*W] of label_dtype (M3_LABEL_F32 truncated as `.long()`, M3_LABEL_I64,
+ * M3_LABEL_U8); 255 = ignored; a value that is neither 255 nor in [0, C) indexes nothing, is treated as ignored and counted in
+ * the record's N_BAD word.  L1 / BCE: f32, the shape AND layout of pred.  Normals: f32 [B,C,H,W] in label_layout.
+ * ws: f32 [m3_loss_ws_elems(B*C*H*W)], no initialisation.  lse (cross-entropy): f32 [B*H*W], written by the forward (the
+ * log-sum-exp of every pixel, ignored ones included) and read by the backward.
+ * record: M3_LOSS_REC_WORDS four-byte words, written by the forward, read by the backward:
+ *   f32 [M3_LOSS_REC_VALUE]    the loss
+ *   f32 [M3_LOSS_REC_COEF]     what the backward multiplies by: CE, L1: 1 / n_valid (0 when n_valid = 0); normals:
+ *                              1 / max(n_valid, 1e-6); BCE: w / numel, the positive elements' factor
+ *   f32 [M3_LOSS_REC_COEF2]    BCE: (1 - w) / numel, the negative elements' factor; else 0
+ *   i32 [M3_LOSS_REC_N_VALID]  CE: pixels with a class; L1, normals: elements with label != 255; BCE: n_pos (label >= 0.5)
+ *   i32 [M3_LOSS_REC_N_AUX]    BCE: n_neg; else 0
+ *   i32 [M3_LOSS_REC_N_BAD]    CE: bad labels; else 0
+ * grad_out: DEVICE f32 scalar, the upstream gradient (a loss scale and 1 / accumulation_steps arrive here).
+ *
+ * CE: loss = mean over valid pixels of lse(x) - x[label] (running maximum: finite at |x| = 6e4), C in [2, 255];
+ *   dpred = (exp(x - lse) - [c == label]) * COEF * grad_out, 0 at ignored pixels.  No valid pixel: loss NaN, dpred 0.
+ * L1: loss = mean of |pred - label| over label != 255; dpred = sign(pred - label) (0 at 0) * COEF * grad_out.  None valid:
+ *   loss NaN, dpred 0.
+ * normals: t = pred / (|pred|_2 over C + 1e-12); loss = sum over label != 255 of |t - label| (norm 1) or (t - label)^2
+ *   (norm 2), / max(n_valid, 1e-6) - 0 when nothing is valid; dpred carries the Jacobian of the normalisation.  C in [1, 8].
+ * BCE: y = label >= 0.5, term = x ([x >= 0] - y) + log(1 + exp(-|x|)); w = pos_weight when has_pos_weight, else
+ *   the fp32 quotient n_neg / (n_pos + n_neg), as the reference's `labels.float()` sums give it, formed in the finalize launch; loss = (w sum_pos + (1 - w) sum_neg) / numel;
+ *   dpred = (sigmoid(x) - y) * (y ? COEF : COEF2) * grad_out. */
+#define M3_LAYOUT_NCHW 0
+#define M3_LAYOUT_NHWC 1
+#define M3_LABEL_F32 0
+#define M3_LABEL_I64 1
+#define M3_LABEL_U8 2
+#define M3_LOSS_MAX_BLOCKS 1024
+#define M3_LOSS_NORMALS_MAX_C 8
+#define M3_LOSS_REC_VALUE 0
+#define M3_LOSS_REC_COEF 1
+#define M3_LOSS_REC_COEF2 2
+#define M3_LOSS_REC_N_VALID 3
+#define M3_LOSS_REC_N_AUX 4
+#define M3_LOSS_REC_N_BAD 5
+#define M3_LOSS_REC_WORDS 8
+int64_t m3_loss_ws_elems(int64_t n);
+int m3_loss_ce_fwd(const void *pred, int dtype, const void *label, int label_dtype, int B, int C, int H, int W, int layout,
+                   float *lse, float *ws, void *record, void *stream);
+int m3_loss_ce_bwd(const void *pred, int dtype, const void *label, int label_dtype, const float *lse, const void *record,
+                   const float *grad_out, int B, int C, int H, int W, int layout, void *dpred, void *stream);
+int m3_loss_l1_fwd(const void *pred, int dtype, const float *label, int B, int C, int H, int W, int layout, float *ws,
+                   void *record, void *stream);
+int m3_loss_l1_bwd(const void *pred, int dtype, const float *label, const void *record, const float *grad_out, int B, int C,
+                   int H, int W, int layout, void *dpred, void *stream);
+int m3_loss_normals_fwd(const void *pred, int dtype, const float *label, int B, int C, int H, int W, int layout,
+                        int label_layout, int norm, float *ws, void *record, void *stream);
+int m3_loss_normals_bwd(const void *pred, int dtype, const float *label, const void *record, const float *grad_out, int B,
+                        int C, int H, int W, int layout, int label_layout, int norm, void *dpred, void *stream);
+int m3_loss_bce_fwd(const void *pred, int dtype, const float *label, int B, int C, int H, int W, int layout,
+                    int has_pos_weight, double pos_weight, float *ws, void *record, void *stream);
+int m3_loss_bce_bwd(const void *pred, int dtype, const float *label, const void *record, const float *grad_out, int B, int C,
+                    int H, int W, int layout, void *dpred, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

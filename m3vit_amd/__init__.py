@@ -20,3 +20,15 @@ def install_fmoe_shim():
     for sub in ("layers", "linear", "functions", "gates", "gates.base_gate", "gates.naive_gate", "distributed"):
         sys.modules["fmoe." + sub] = importlib.import_module("m3vit_amd.fmoe." + sub)
     return pkg
+
+
+_LOSS_NAMES = ("SoftMaxwithLoss", "BalancedCrossEntropyLoss", "DepthLoss", "NormalsLoss", "SingleTaskLoss", "MultiTaskLoss",
+               "get_loss")
+
+
+def __getattr__(name):
+    """the criterion modules of m3vit_amd.losses, importable from the package (loaded on first use: they need torch)"""
+    if name in _LOSS_NAMES:
+        from . import losses
+        return getattr(losses, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("M3VIT_LIB") or os.path.join(_HERE, "libm3vit_hip.so")   # M3VIT_LIB: diagnostic builds
@@ -16,6 +16,11 @@ M3_F32, M3_F16, M3_BF16 = 0, 1, 2
 M3_ACT_NONE, M3_ACT_GELU = 0, 1
 M3_OPTIM_ADAMW, M3_OPTIM_ADAM, M3_OPTIM_SGD = 0, 1, 2
 M3_OPTIM_CHUNK, M3_OPTIM_HYPER, M3_OPTIM_DECOUPLED, M3_OPTIM_NESTEROV = 4096, 8, 1, 2
+M3_LAYOUT_NCHW, M3_LAYOUT_NHWC = 0, 1
+M3_LABEL_F32, M3_LABEL_I64, M3_LABEL_U8 = 0, 1, 2
+M3_LOSS_MAX_BLOCKS, M3_LOSS_NORMALS_MAX_C, M3_LOSS_REC_WORDS = 1024, 8, 8
+(M3_LOSS_REC_VALUE, M3_LOSS_REC_COEF, M3_LOSS_REC_COEF2, M3_LOSS_REC_N_VALID, M3_LOSS_REC_N_AUX,
+ M3_LOSS_REC_N_BAD) = range(6)
 
 
 class M3Error(RuntimeError):
@@ -200,6 +205,15 @@ SIGNATURES = {
     "m3_optim_state_elems": (c_int, [_I]),
     "m3_optim_prepare": (c_int, [_V, _I, _I, _V, _I, _I, _V, _V, _F, _I, _V, _V, _V]),
     "m3_optim_step": (c_int, [_V, _I, _I, _V, _V, _I, _V]),
+    "m3_loss_ws_elems": (c_int64, [_L]),
+    "m3_loss_ce_fwd": (c_int, [_V, _I, _V, _I, _I, _I, _I, _I, _I, _V, _V, _V, _V]),
+    "m3_loss_ce_bwd": (c_int, [_V, _I, _V, _I, _V, _V, _V, _I, _I, _I, _I, _I, _V, _V]),
+    "m3_loss_l1_fwd": (c_int, [_V, _I, _V, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "m3_loss_l1_bwd": (c_int, [_V, _I, _V, _V, _V, _I, _I, _I, _I, _I, _V, _V]),
+    "m3_loss_normals_fwd": (c_int, [_V, _I, _V, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "m3_loss_normals_bwd": (c_int, [_V, _I, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _V, _V]),
+    "m3_loss_bce_fwd": (c_int, [_V, _I, _V, _I, _I, _I, _I, _I, _I, c_double, _V, _V, _V]),
+    "m3_loss_bce_bwd": (c_int, [_V, _I, _V, _V, _V, _I, _I, _I, _I, _I, _V, _V]),
     "m3_cast_f32": (c_int, [_V, _L, _V, _I, _V]),
     "m3_scale_rows_cast": (c_int, [_V, _L, _I, _V, _I, _V, _I, _V]),
     "m3_im2row": (c_int, [_V, _I, _I, _I, _I, _I, _V, _I, _V]),

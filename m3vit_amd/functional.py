@@ -341,3 +341,91 @@ class GroupedFFNFn(torch.autograd.Function):
         dx = torch.empty(T, D, dtype=torch.float32, device=dev)
         ops.combine_fwd(dxe, torch.ones_like(sc), None, dx)
         return dx.to(dt), None, dscore, dw1, db1, dw2, db2
+
+
+# ------------------------------------------------------------------------------------------- dense-prediction losses
+# One Function per loss of csrc/loss.hip.  forward: two launches, returns (loss, record) - the loss a 0-dim fp32 VIEW into the
+# device-resident record, the record itself non-differentiable (counts, coefficients, bad-label count: include/m3vit_hip.h).
+# backward: one launch that reads grad_output through its device pointer (a GradScaler's scale and a division by the
+# accumulation steps arrive there) - no .item(), no bool(), no masked_select anywhere.  Labels get no gradient.
+
+def _loss_value(record):
+    return record[:1].view(torch.float32).view(())
+
+
+def _upstream(g):
+    return g.detach().to(torch.float32).reshape(1)
+
+
+class SoftmaxCrossEntropyFn(torch.autograd.Function):
+    """losses/loss_functions.py:16-33 (LogSoftmax + NLLLoss(ignore_index=255)); saves pred, label, the record and the per-pixel
+    log-sum-exp (1 / C of the logits), so the backward is a single pass."""
+
+    @staticmethod
+    def forward(ctx, pred, label):
+        p, _ = ops.loss_layout(pred)
+        lab = label.detach().contiguous()
+        record, lse = ops.loss_ce_fwd(p, lab)
+        ctx.save_for_backward(p, lab, record, lse)
+        ctx.mark_non_differentiable(record)
+        return _loss_value(record), record
+
+    @staticmethod
+    def backward(ctx, g, _g_record):
+        p, lab, record, lse = ctx.saved_tensors
+        return ops.loss_ce_bwd(p, lab, lse, record, _upstream(g)), None
+
+
+class MaskedL1Fn(torch.autograd.Function):
+    """losses/loss_functions.py:126-140 (DepthLoss('l1'))"""
+
+    @staticmethod
+    def forward(ctx, pred, label):
+        p, layout = ops.loss_layout(pred)
+        lab = ops.loss_label_like(label.detach(), p, layout)      # converted once; the backward reads the same tensor
+        record = ops.loss_l1_fwd(p, lab)
+        ctx.save_for_backward(p, lab, record)
+        ctx.mark_non_differentiable(record)
+        return _loss_value(record), record
+
+    @staticmethod
+    def backward(ctx, g, _g_record):
+        p, lab, record = ctx.saved_tensors
+        return ops.loss_l1_bwd(p, lab, record, _upstream(g)), None
+
+
+class NormalsLossFn(torch.autograd.Function):
+    """losses/loss_functions.py:143-197 (NormalsLoss(normalize=True, size_average=True, norm))"""
+
+    @staticmethod
+    def forward(ctx, pred, label, norm):
+        p, _ = ops.loss_layout(pred)
+        lab = label.detach()
+        record = ops.loss_normals_fwd(p, lab, norm)
+        ctx.save_for_backward(p, lab, record)
+        ctx.norm = norm
+        ctx.mark_non_differentiable(record)
+        return _loss_value(record), record
+
+    @staticmethod
+    def backward(ctx, g, _g_record):
+        p, lab, record = ctx.saved_tensors
+        return ops.loss_normals_bwd(p, lab, record, _upstream(g), ctx.norm), None, None
+
+
+class BalancedBCEFn(torch.autograd.Function):
+    """losses/loss_functions.py:36-84 (BalancedCrossEntropyLoss(size_average=True, pos_weight), no void_pixels)"""
+
+    @staticmethod
+    def forward(ctx, pred, label, pos_weight):
+        p, layout = ops.loss_layout(pred)
+        lab = ops.loss_label_like(label.detach(), p, layout)
+        record = ops.loss_bce_fwd(p, lab, pos_weight)
+        ctx.save_for_backward(p, lab, record)
+        ctx.mark_non_differentiable(record)
+        return _loss_value(record), record
+
+    @staticmethod
+    def backward(ctx, g, _g_record):
+        p, lab, record = ctx.saved_tensors
+        return ops.loss_bce_bwd(p, lab, record, _upstream(g)), None, None

@@ -994,6 +994,192 @@ class OptimPlan:
         return self.state[3]
 
 
+# ---------------------------------------------------------------------------- dense-prediction losses (csrc/loss.hip)
+LOSS_REC_WORDS = _lib.M3_LOSS_REC_WORDS
+_LABEL_DT = {torch.float32: _lib.M3_LABEL_F32, torch.int64: _lib.M3_LABEL_I64, torch.uint8: _lib.M3_LABEL_U8}
+
+
+def loss_ws_elems(n: int) -> int:
+    """fp32 elements of the partials workspace of a loss forward over a pred of n elements (m3_loss_ws_elems)"""
+    return int(lib().m3_loss_ws_elems(n))
+
+
+def loss_layout(pred, name="pred"):
+    """(pred as the kernels read it, layout code).  A 4-d CUDA tensor of an activation dtype; NCHW-contiguous and
+    channels-last storage are read in place, a pred in neither layout is made NCHW-contiguous (one copy) - the gradient then
+    comes back contiguous."""
+    if not isinstance(pred, torch.Tensor):
+        raise _lib.M3Error(f"{name} must be a tensor, got {type(pred).__name__}")
+    if not pred.is_cuda:
+        raise _lib.M3Error(f"{name} must live on the GPU (no CPU path)")
+    if pred.dim() != 4 or pred.numel() == 0:
+        raise _lib.M3Error(f"{name} must be a non-empty [B, C, H, W] tensor, got shape {tuple(pred.shape)}")
+    dt_code(pred.dtype)
+    if pred.is_contiguous():
+        return pred, _lib.M3_LAYOUT_NCHW
+    if pred.is_contiguous(memory_format=torch.channels_last):
+        return pred, _lib.M3_LAYOUT_NHWC
+    return pred.contiguous(), _lib.M3_LAYOUT_NCHW
+
+
+def _loss_bufs(pred, ws, record):
+    need = loss_ws_elems(pred.numel())
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.float32, device=pred.device)
+    _req(ws, torch.float32, "ws", min_numel=need)
+    if record is None:
+        record = torch.empty(LOSS_REC_WORDS, dtype=torch.int32, device=pred.device)
+    _req(record, torch.int32, "record", numel=LOSS_REC_WORDS)
+    return ws, record
+
+
+def _loss_bwd_bufs(pred, layout, record, grad_out, dpred):
+    _req(record, torch.int32, "record", numel=LOSS_REC_WORDS)
+    _req(grad_out, torch.float32, "grad_out", numel=1)
+    fmt = torch.channels_last if layout == _lib.M3_LAYOUT_NHWC else torch.contiguous_format
+    if dpred is None:
+        dpred = torch.empty_like(pred, memory_format=fmt)
+    if not dpred.is_cuda or dpred.dtype != pred.dtype or dpred.shape != pred.shape or not dpred.is_contiguous(memory_format=fmt):
+        raise _lib.M3Error(f"dpred must have pred's dtype, shape and layout ({pred.dtype}, {tuple(pred.shape)}), got "
+                           f"{dpred.dtype}, {tuple(dpred.shape)}, strides {tuple(dpred.stride())}")
+    return dpred
+
+
+def _class_label(label, pred, name="label"):
+    B, C, H, W = pred.shape
+    if not isinstance(label, torch.Tensor) or label.dtype not in _LABEL_DT:
+        raise _lib.M3Error(f"{name} must be a float32, int64 or uint8 tensor")
+    if tuple(label.shape) not in ((B, 1, H, W), (B, H, W)):
+        raise _lib.M3Error(f"{name} must be [{B}, 1, {H}, {W}] or [{B}, {H}, {W}], got {tuple(label.shape)}")
+    _req(label, name=name, numel=B * H * W)
+    if not 2 <= C <= 255:
+        raise _lib.M3Error(f"cross-entropy takes 2 <= C <= 255 classes, got {C}")
+    return label
+
+
+def loss_label_like(label, pred, layout, name="label"):
+    """an fp32 label of pred's shape, in pred's layout (L1 / BCE read both as one flat span): a label in the other layout is
+    copied once - only possible for C > 1, which none of the reference's depth / edge / saliency heads has"""
+    if not isinstance(label, torch.Tensor) or not label.is_cuda:
+        raise _lib.M3Error(f"{name} must be a GPU tensor (no CPU path)")
+    if label.dtype != torch.float32 or label.shape != pred.shape:
+        raise _lib.M3Error(f"{name} must be float32 of pred's shape {tuple(pred.shape)}, got {label.dtype} {tuple(label.shape)}")
+    fmt = torch.channels_last if layout == _lib.M3_LAYOUT_NHWC else torch.contiguous_format
+    return label if label.is_contiguous(memory_format=fmt) else label.contiguous(memory_format=fmt)
+
+
+def loss_ce_fwd(pred, label, *, lse=None, ws=None, record=None):
+    """Pixel-wise softmax cross-entropy (m3_loss_ce_fwd).  pred [B,C,H,W] fp32 / fp16 / bf16, NCHW or channels-last (see
+    loss_layout); label [B,1,H,W] or [B,H,W] float32 / int64 / uint8, 255 = ignored.  Returns (record, lse): the int32 record
+    (layout: include/m3vit_hip.h) and the per-pixel log-sum-exp [B,H,W] the backward reads.  Nothing is read back."""
+    pred, layout = loss_layout(pred)
+    B, C, H, W = pred.shape
+    _class_label(label, pred)
+    ws, record = _loss_bufs(pred, ws, record)
+    if lse is None:
+        lse = torch.empty(B, H, W, dtype=torch.float32, device=pred.device)
+    _req(lse, torch.float32, "lse", numel=B * H * W)
+    check(lib().m3_loss_ce_fwd(_p(pred), dt_code(pred.dtype), _p(label), _LABEL_DT[label.dtype], B, C, H, W, layout, _p(lse),
+                               _p(ws), _p(record), _stream()), "m3_loss_ce_fwd")
+    return record, lse
+
+
+def loss_ce_bwd(pred, label, lse, record, grad_out, *, dpred=None):
+    """d pred of loss_ce_fwd, scaled by the 0-dim float32 GPU tensor grad_out (read on the device); in pred's dtype and layout"""
+    pred, layout = loss_layout(pred)
+    B, C, H, W = pred.shape
+    _class_label(label, pred)
+    _req(lse, torch.float32, "lse", numel=B * H * W)
+    dpred = _loss_bwd_bufs(pred, layout, record, grad_out, dpred)
+    check(lib().m3_loss_ce_bwd(_p(pred), dt_code(pred.dtype), _p(label), _LABEL_DT[label.dtype], _p(lse), _p(record),
+                               _p(grad_out), B, C, H, W, layout, _p(dpred), _stream()), "m3_loss_ce_bwd")
+    return dpred
+
+
+def loss_l1_fwd(pred, label, *, ws=None, record=None):
+    """Masked L1 (m3_loss_l1_fwd): mean |pred - label| over label != 255.  label: float32 of pred's shape.  Returns record."""
+    pred, layout = loss_layout(pred)
+    B, C, H, W = pred.shape
+    label = loss_label_like(label, pred, layout)
+    ws, record = _loss_bufs(pred, ws, record)
+    check(lib().m3_loss_l1_fwd(_p(pred), dt_code(pred.dtype), _p(label), B, C, H, W, layout, _p(ws), _p(record), _stream()),
+          "m3_loss_l1_fwd")
+    return record
+
+
+def loss_l1_bwd(pred, label, record, grad_out, *, dpred=None):
+    pred, layout = loss_layout(pred)
+    B, C, H, W = pred.shape
+    label = loss_label_like(label, pred, layout)
+    dpred = _loss_bwd_bufs(pred, layout, record, grad_out, dpred)
+    check(lib().m3_loss_l1_bwd(_p(pred), dt_code(pred.dtype), _p(label), _p(record), _p(grad_out), B, C, H, W, layout,
+                               _p(dpred), _stream()), "m3_loss_l1_bwd")
+    return dpred
+
+
+def _normals_label(label, pred):
+    if not isinstance(label, torch.Tensor) or not label.is_cuda:
+        raise _lib.M3Error("label must be a GPU tensor (no CPU path)")
+    if label.dtype != torch.float32 or label.shape != pred.shape:
+        raise _lib.M3Error(f"label must be float32 of pred's shape {tuple(pred.shape)}, got {label.dtype} {tuple(label.shape)}")
+    if not 1 <= pred.shape[1] <= _lib.M3_LOSS_NORMALS_MAX_C:
+        raise _lib.M3Error(f"the normals loss takes 1 <= C <= {_lib.M3_LOSS_NORMALS_MAX_C}, got {pred.shape[1]}")
+    if label.is_contiguous():
+        return label, _lib.M3_LAYOUT_NCHW
+    if label.is_contiguous(memory_format=torch.channels_last):
+        return label, _lib.M3_LAYOUT_NHWC
+    return label.contiguous(), _lib.M3_LAYOUT_NCHW
+
+
+def loss_normals_fwd(pred, label, norm=1, *, ws=None, record=None):
+    """Normalised normals loss (m3_loss_normals_fwd): t = pred / (|pred|_2 + 1e-12) over C, sum of |t - label| (norm 1) or
+    (t - label)^2 (norm 2) over label != 255, / max(n_valid, 1e-6).  pred and label each in either layout.  Returns record."""
+    if norm not in (1, 2):
+        raise _lib.M3Error(f"norm must be 1 or 2, got {norm}")
+    pred, layout = loss_layout(pred)
+    B, C, H, W = pred.shape
+    label, ll = _normals_label(label, pred)
+    ws, record = _loss_bufs(pred, ws, record)
+    check(lib().m3_loss_normals_fwd(_p(pred), dt_code(pred.dtype), _p(label), B, C, H, W, layout, ll, norm, _p(ws), _p(record),
+                                    _stream()), "m3_loss_normals_fwd")
+    return record
+
+
+def loss_normals_bwd(pred, label, record, grad_out, norm=1, *, dpred=None):
+    if norm not in (1, 2):
+        raise _lib.M3Error(f"norm must be 1 or 2, got {norm}")
+    pred, layout = loss_layout(pred)
+    B, C, H, W = pred.shape
+    label, ll = _normals_label(label, pred)
+    dpred = _loss_bwd_bufs(pred, layout, record, grad_out, dpred)
+    check(lib().m3_loss_normals_bwd(_p(pred), dt_code(pred.dtype), _p(label), _p(record), _p(grad_out), B, C, H, W, layout, ll,
+                                    norm, _p(dpred), _stream()), "m3_loss_normals_bwd")
+    return dpred
+
+
+def loss_bce_fwd(pred, label, pos_weight=None, *, ws=None, record=None):
+    """Balanced binary cross-entropy (m3_loss_bce_fwd), size_average: labels = label >= 0.5, w = pos_weight or, for None,
+    n_neg / (n_pos + n_neg) formed on the device.  label: float32 of pred's shape.  Returns record."""
+    pred, layout = loss_layout(pred)
+    B, C, H, W = pred.shape
+    label = loss_label_like(label, pred, layout)
+    ws, record = _loss_bufs(pred, ws, record)
+    check(lib().m3_loss_bce_fwd(_p(pred), dt_code(pred.dtype), _p(label), B, C, H, W, layout, 0 if pos_weight is None else 1,
+                                0.0 if pos_weight is None else float(pos_weight), _p(ws), _p(record), _stream()),
+          "m3_loss_bce_fwd")
+    return record
+
+
+def loss_bce_bwd(pred, label, record, grad_out, *, dpred=None):
+    pred, layout = loss_layout(pred)
+    B, C, H, W = pred.shape
+    label = loss_label_like(label, pred, layout)
+    dpred = _loss_bwd_bufs(pred, layout, record, grad_out, dpred)
+    check(lib().m3_loss_bce_bwd(_p(pred), dt_code(pred.dtype), _p(label), _p(record), _p(grad_out), B, C, H, W, layout,
+                                _p(dpred), _stream()), "m3_loss_bce_bwd")
+    return dpred
+
+
 def cast_f32(src, dst):
     _req(src, torch.float32, "src"); _act(dst, "dst", src.numel())
     check(lib().m3_cast_f32(_p(src), src.numel(), _p(dst), dt_code(dst.dtype), _stream()), "m3_cast_f32")
