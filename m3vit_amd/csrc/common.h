@@ -178,6 +178,31 @@ template <> struct Vec8<bf16_t> {
   }
 };
 
+// V consecutive elements of T <-> V floats, for kernels that keep their values as float arrays: V = 1 a scalar access,
+// V = 4 and 8 the accesses of Vec4 / Vec8
+template <typename T, int V> struct Pack;
+template <typename T> struct Pack<T, 1> {
+  static __device__ __forceinline__ void load(const T *p, float (&v)[1]) { v[0] = (float)*p; }
+  static __device__ __forceinline__ void store(T *p, const float (&v)[1]) { *p = (T)v[0]; }
+};
+template <typename T> struct Pack<T, 4> {
+  static __device__ __forceinline__ void load(const T *p, float (&v)[4]) {
+    const f32x4 a = Vec4<T>::load(p);
+    v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
+  }
+  static __device__ __forceinline__ void store(T *p, const float (&v)[4]) { Vec4<T>::store(p, f32x4{v[0], v[1], v[2], v[3]}); }
+};
+template <typename T> struct Pack<T, 8> {
+  static __device__ __forceinline__ void load(const T *p, float (&v)[8]) {
+    f32x4 a, b;
+    Vec8<T>::load(p, a, b);
+    v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
+  }
+  static __device__ __forceinline__ void store(T *p, const float (&v)[8]) {
+    Vec8<T>::store(p, f32x4{v[0], v[1], v[2], v[3]}, f32x4{v[4], v[5], v[6], v[7]});
+  }
+};
+
 // erf-GELU (nn.GELU default) and its derivative.  erfc is evaluated with Abramowitz-Stegun 7.1.26
 // (|abs error| <= 1.5e-7, i.e. at the fp32 rounding level of the surrounding MFMA sums) instead
 // of the ~40-instruction libm erff: in the GEMM epilogues the libm version cost as much as the
@@ -241,5 +266,31 @@ int launch_reduce_rows_i32(const int32_t *part, int nrows, int N, int G, int64_t
 
 static inline int dtype_size(int dt) { return (dt == M3_F16 || dt == M3_BF16) ? 2 : 4; }
 static inline bool dtype_ok(int dt) { return dt == M3_F32 || dt == M3_F16 || dt == M3_BF16; }
+
+// --------------------------------------------------------------- host: run-time value -> template instance
+// An entry point validates, computes grid and LDS, then names its kernel ONCE inside a generic lambda; these two choose the
+// instance:
+//   by_dtype(dtype, [&](auto tt) {
+//     typedef typename decltype(tt)::type T;
+//     auto go = [&](auto kt) { hipLaunchKernelGGL((kernel<T, decltype(kt)::value>), ...); };
+//     if (!by_int<4, 2, 1, 8>(k, go)) go(IntTag<0>{});
+//   });
+// Every (type, constant) pair the lambdas can reach is instantiated, so the listed constants ARE the set of built kernels.
+template <typename T> struct DtypeTag { typedef T type; };
+template <int N> struct IntTag { static constexpr int value = N; };
+
+// f(DtypeTag<T>{}), T the element type of a dtype code that dtype_ok() has accepted
+template <typename F> static inline void by_dtype(int dt, F &&f) {
+  if (dt == M3_F16) f(DtypeTag<half_t>{});
+  else if (dt == M3_BF16) f(DtypeTag<bf16_t>{});
+  else f(DtypeTag<float>{});
+}
+// f(IntTag<N>{}) for the listed N that equals v; false, and nothing called, when none does: the fallback is the caller's
+template <int... Ns, typename F> static inline bool by_int(int v, F &&f) {
+  return ((v == Ns ? (f(IntTag<Ns>{}), true) : false) || ...);
+}
+
+constexpr int ROW_THREADS = 256;   // row kernels: 4 waves = 4 rows per workgroup
+static inline unsigned row_blocks(int64_t T) { return (unsigned)((T + 3) / 4); }
 
 }  // namespace m3

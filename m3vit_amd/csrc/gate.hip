@@ -704,30 +704,6 @@ using namespace m3;
 extern "C" int m3_gate_num_blocks(int64_t T) { return (int)((T + GATE_TOK - 1) / GATE_TOK); }
 extern "C" int m3_gate_dw_blocks(int64_t T) { return (int)((T + GATE_DW_TOK - 1) / GATE_DW_TOK); }
 
-template <typename T, int EP, int EW>
-static void launch_gate_fwd_e(bool exact, dim3 grid, hipStream_t s, const GateFwdDev &d) {
-  constexpr int NT = GATE_TOK * (EP / EW);
-  const int rowb = d.D * (int)sizeof(T);
-  if (exact && rowb == 6 * GATE_ROWB) hipLaunchKernelGGL((gate_fwd_kernel<T, EP, EW, true, 6>), grid, dim3(NT), 0, s, d);
-  else if (exact && rowb == 12 * GATE_ROWB) hipLaunchKernelGGL((gate_fwd_kernel<T, EP, EW, true, 12>), grid, dim3(NT), 0, s, d);
-  else if (exact) hipLaunchKernelGGL((gate_fwd_kernel<T, EP, EW, true, 0>), grid, dim3(NT), 0, s, d);
-  else hipLaunchKernelGGL((gate_fwd_kernel<T, EP, EW, false, 0>), grid, dim3(NT), 0, s, d);
-}
-
-template <typename T>
-static int launch_gate_fwd(int epad, dim3 grid, hipStream_t s, const GateFwdDev &d) {
-  const bool exact = d.E == epad;
-  switch (epad) {
-    case 4: launch_gate_fwd_e<T, 4, 4>(exact, grid, s, d); break;
-    case 8: launch_gate_fwd_e<T, 8, 4>(exact, grid, s, d); break;
-    case 16: launch_gate_fwd_e<T, 16, 4>(exact, grid, s, d); break;
-    case 32: launch_gate_fwd_e<T, 32, 8>(exact, grid, s, d); break;
-    case 64: launch_gate_fwd_e<T, 64, 16>(exact, grid, s, d); break;
-    default: return M3_ERR_UNSUPPORTED;
-  }
-  return check_launch("m3_gate_fwd");
-}
-
 static int epad_of(int E) { return E <= 4 ? 4 : E <= 8 ? 8 : E <= 16 ? 16 : E <= 32 ? 32 : 64; }
 static int epad8_of(int E) { return E <= 8 ? 8 : E <= 16 ? 16 : E <= 32 ? 32 : 64; }
 
@@ -753,9 +729,24 @@ extern "C" int m3_gate_fwd(const m3_gate_fwd_args *a, void *stream) {
   d.part_count = a->part_count;
   const dim3 grid((unsigned)m3_gate_num_blocks(a->T));
   hipStream_t s = (hipStream_t)stream;
-  if (a->x_dtype == M3_F16) return launch_gate_fwd<half_t>(epad_of(a->E), grid, s, d);
-  else if (a->x_dtype == M3_BF16) return launch_gate_fwd<bf16_t>(epad_of(a->E), grid, s, d);
-  return launch_gate_fwd<float>(epad_of(a->E), grid, s, d);
+  // instance: E padded to 4 .. 64 with 4 / 4 / 4 / 8 / 16 experts per wave; exact E or padded; rows of exactly 6 or 12 steps
+  // (exact E only) fetched whole up front
+  const int epad = epad_of(a->E), rowb = a->D * es;
+  const bool exact = a->E == epad;
+  const int ns = rowb % GATE_ROWB == 0 ? rowb / GATE_ROWB : 0;
+  by_dtype(a->x_dtype, [&](auto tt) {
+    typedef typename decltype(tt)::type T;
+    by_int<4, 8, 16, 32, 64>(epad, [&](auto ep) {
+      constexpr int EP = decltype(ep)::value, EW = EP <= 16 ? 4 : EP / 4;
+      auto go = [&](auto ex, auto nst) {
+        hipLaunchKernelGGL((gate_fwd_kernel<T, EP, EW, decltype(ex)::value != 0, decltype(nst)::value>), grid,
+                           dim3(GATE_TOK * (EP / EW)), 0, s, d);
+      };
+      if (!exact) go(IntTag<0>{}, IntTag<0>{});
+      else if (!by_int<6, 12>(ns, [&](auto nst) { go(IntTag<1>{}, nst); })) go(IntTag<1>{}, IntTag<0>{});
+    });
+  });
+  return check_launch("m3_gate_fwd");
 }
 
 extern "C" int m3_gate_reduce(const float *part_importance, const int32_t *part_load, int nblk, int E,
@@ -819,13 +810,9 @@ extern "C" int m3_gate_bwd_logits(const m3_gate_bwd_args *a, void *stream) {
   M3_REQUIRE(!a->d_logits_act || dtype_ok(a->act_dtype), "m3_gate_bwd_logits: bad dtype of the second copy");
   const dim3 grid((unsigned)((a->T + 255) / 256));
   hipStream_t s = (hipStream_t)stream;
-  switch (epad_of(a->E)) {
-    case 4: hipLaunchKernelGGL(gate_bwd_logits_kernel<4>, grid, dim3(256), 0, s, d); break;
-    case 8: hipLaunchKernelGGL(gate_bwd_logits_kernel<8>, grid, dim3(256), 0, s, d); break;
-    case 16: hipLaunchKernelGGL(gate_bwd_logits_kernel<16>, grid, dim3(256), 0, s, d); break;
-    case 32: hipLaunchKernelGGL(gate_bwd_logits_kernel<32>, grid, dim3(256), 0, s, d); break;
-    default: hipLaunchKernelGGL(gate_bwd_logits_kernel<64>, grid, dim3(256), 0, s, d); break;
-  }
+  by_int<4, 8, 16, 32, 64>(epad_of(a->E), [&](auto ep) {
+    hipLaunchKernelGGL(gate_bwd_logits_kernel<decltype(ep)::value>, grid, dim3(256), 0, s, d);
+  });
   return check_launch("m3_gate_bwd_logits");
 }
 
@@ -853,36 +840,30 @@ extern "C" int m3_gate_bwd_params(const void *x, int x_dtype, int64_t T, int D, 
     if (ep <= 16 && D % 4 == 0 && (D / 4) * rpn <= 512 && ((uintptr_t)x % 8) == 0 && (ldx * es) % 8 == 0 &&
         lds4 <= 144 * 1024) {
       const dim3 grid4(nblk), block4((D / 4) * rpn);
-#define M3_DW4_CASE(TT, EP)                                                                                                  \
-  do {                                                                                                                       \
-    static bool attr = false;                                                                                                \
-    if (!attr) { (void)hipFuncSetAttribute((const void *)gate_bwd_dw4_kernel<TT, EP>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024); attr = true; } \
-    hipLaunchKernelGGL((gate_bwd_dw4_kernel<TT, EP>), grid4, block4, lds4, s, (const char *)x, T, D, ldx * es, d_logits, E, part_dw); \
-  } while (0)
-      if (x_dtype == M3_F16) { if (ep == 8) M3_DW4_CASE(half_t, 8); else M3_DW4_CASE(half_t, 16); }
-      else if (x_dtype == M3_BF16) { if (ep == 8) M3_DW4_CASE(bf16_t, 8); else M3_DW4_CASE(bf16_t, 16); }
-      else { if (ep == 8) M3_DW4_CASE(float, 8); else M3_DW4_CASE(float, 16); }
-#undef M3_DW4_CASE
+      by_dtype(x_dtype, [&](auto tt) {
+        typedef typename decltype(tt)::type TT;
+        auto go = [&](auto e) {
+          constexpr int EP = decltype(e)::value;
+          static bool attr = false;                        // once per instance: every (TT, EP) has its own `go`
+          if (!attr) { (void)hipFuncSetAttribute((const void *)gate_bwd_dw4_kernel<TT, EP>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024); attr = true; }
+          hipLaunchKernelGGL((gate_bwd_dw4_kernel<TT, EP>), grid4, block4, lds4, s, (const char *)x, T, D, ldx * es, d_logits, E, part_dw);
+        };
+        if (!by_int<8>(ep, go)) go(IntTag<16>{});
+      });
       int rc4 = check_launch("m3_gate_bwd_params(dw4)");
       if (rc4) return rc4;
       rc4 = launch_reduce_rows_f32(part_dw, nblk, (int)elems, 1, 0, d_w_gate, beta_dw, s);
       if (rc4) return rc4;
     } else {
     const dim3 grid(nblk), block(((D + 63) / 64) * 64);
-#define M3_DW_CASE(TT, EP)                                                                                     \
-  hipLaunchKernelGGL((gate_bwd_dw_kernel<TT, EP>), grid, block, 0, s, (const char *)x, T, D, ldx * es, d_logits, \
-                     E, part_dw)
-    if (x_dtype == M3_F16) {
-      if (ep == 8) M3_DW_CASE(half_t, 8); else if (ep == 16) M3_DW_CASE(half_t, 16);
-      else if (ep == 32) M3_DW_CASE(half_t, 32); else M3_DW_CASE(half_t, 64);
-    } else if (x_dtype == M3_BF16) {
-      if (ep == 8) M3_DW_CASE(bf16_t, 8); else if (ep == 16) M3_DW_CASE(bf16_t, 16);
-      else if (ep == 32) M3_DW_CASE(bf16_t, 32); else M3_DW_CASE(bf16_t, 64);
-    } else {
-      if (ep == 8) M3_DW_CASE(float, 8); else if (ep == 16) M3_DW_CASE(float, 16);
-      else if (ep == 32) M3_DW_CASE(float, 32); else M3_DW_CASE(float, 64);
-    }
-#undef M3_DW_CASE
+    by_dtype(x_dtype, [&](auto tt) {
+      typedef typename decltype(tt)::type TT;
+      auto go = [&](auto e) {
+        hipLaunchKernelGGL((gate_bwd_dw_kernel<TT, decltype(e)::value>), grid, block, 0, s, (const char *)x, T, D, ldx * es,
+                           d_logits, E, part_dw);
+      };
+      if (!by_int<8, 16, 32>(ep, go)) go(IntTag<64>{});
+    });
     int rc = check_launch("m3_gate_bwd_params(dw)");
     if (rc) return rc;
     hipLaunchKernelGGL(gate_dw_reduce_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, s, part_dw, nblk,
@@ -896,10 +877,11 @@ extern "C" int m3_gate_bwd_params(const void *x, int x_dtype, int64_t T, int D, 
     int64_t blocks = (T + 3) / 4;
     if (blocks > 2048) blocks = 2048;
     const dim3 grid((unsigned)blocks), block(256);
-#define M3_DX_CASE(EP) \
-  hipLaunchKernelGGL((gate_bwd_dx_kernel<EP>), grid, block, lds, s, d_logits, w_gate, T, D, E, dx, lddx, beta_dx)
-    if (ep == 8) M3_DX_CASE(8); else if (ep == 16) M3_DX_CASE(16); else if (ep == 32) M3_DX_CASE(32); else M3_DX_CASE(64);
-#undef M3_DX_CASE
+    auto go = [&](auto e) {
+      hipLaunchKernelGGL((gate_bwd_dx_kernel<decltype(e)::value>), grid, block, lds, s, d_logits, w_gate, T, D, E, dx, lddx,
+                         beta_dx);
+    };
+    if (!by_int<8, 16, 32>(ep, go)) go(IntTag<64>{});
     return check_launch("m3_gate_bwd_params(dx)");
   }
   return M3_OK;

@@ -23,20 +23,6 @@ constexpr int LS_CCHUNK = 8;                        // channels of a planar pixe
 
 enum { K_CE = 0, K_L1 = 1, K_NORMALS = 2, K_BCE = 3 };
 
-// V consecutive elements of T <-> floats
-template <typename T, int V> struct Pack;
-template <typename T> struct Pack<T, 1> {
-  static __device__ __forceinline__ void load(const T *p, float (&v)[1]) { v[0] = (float)*p; }
-  static __device__ __forceinline__ void store(T *p, const float (&v)[1]) { *p = (T)v[0]; }
-};
-template <typename T> struct Pack<T, 4> {
-  static __device__ __forceinline__ void load(const T *p, float (&v)[4]) {
-    const f32x4 a = Vec4<T>::load(p);
-    v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
-  }
-  static __device__ __forceinline__ void store(T *p, const float (&v)[4]) { Vec4<T>::store(p, f32x4{v[0], v[1], v[2], v[3]}); }
-};
-
 // the class of pixel i as the reference's `label[:, 0].long()` sees it (truncation), or -1 for a value that is no class
 // index at all.  Returns [0, 255] or -1: 255 is "ignore", [0, C) a class, everything else a bad label.  L, the label dtype, is
 // a template constant of every cross-entropy kernel: a run-time switch would put each label load into a basic block of its own,
@@ -552,19 +538,10 @@ static int finalize(const float *ws, int nblk, int kind, double numel, int has_p
   return check_launch(who);
 }
 
-#define LOSS_BY_LABEL(ldt, CALL)                                           \
-  do {                                                                     \
-    if ((ldt) == M3_LABEL_I64) { constexpr int L = M3_LABEL_I64; CALL; }   \
-    else if ((ldt) == M3_LABEL_U8) { constexpr int L = M3_LABEL_U8; CALL; } \
-    else { constexpr int L = M3_LABEL_F32; CALL; }                         \
-  } while (0)
-
-#define LOSS_BY_DTYPE(dt, CALL)                          \
-  do {                                                   \
-    if ((dt) == M3_F32) { typedef float T; CALL; }       \
-    else if ((dt) == M3_F16) { typedef half_t T; CALL; } \
-    else { typedef bf16_t T; CALL; }                     \
-  } while (0)
+// f(IntTag<L>{}), L the label dtype code that label_dtype_ok() has accepted
+template <typename F> static inline void by_label(int ldt, F &&f) {
+  if (!by_int<M3_LABEL_I64, M3_LABEL_U8>(ldt, f)) f(IntTag<M3_LABEL_F32>{});
+}
 
 static inline int group_shift(int nch) {                 // lanes per channels-last pixel: the power of two >= nch, at most 64
   int sh = 0;
@@ -595,12 +572,16 @@ extern "C" int m3_loss_ce_fwd(const void *pred, int dtype, const void *label, in
     const bool vec = aligned16(pred) && aligned16(lse) && sh.HW % 4 == 0;
     const int units = vec ? sh.npix / 4 : sh.npix;
     nblk = blocks_for(units, LS_THREADS);
-    LOSS_BY_DTYPE(dtype, LOSS_BY_LABEL(label_dtype, {
-      if (vec) hipLaunchKernelGGL((ce_fwd_planar_kernel<T, 4, L>), dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label,
-                                  C, sh.HW, units, lse, ws);
-      else hipLaunchKernelGGL((ce_fwd_planar_kernel<T, 1, L>), dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label,
-                              C, sh.HW, units, lse, ws);
-    }));
+    by_dtype(dtype, [&](auto tt) {
+      typedef typename decltype(tt)::type T;
+      by_label(label_dtype, [&](auto lt) {
+        auto go = [&](auto v) {
+          hipLaunchKernelGGL((ce_fwd_planar_kernel<T, decltype(v)::value, decltype(lt)::value>), dim3(nblk), dim3(LS_THREADS), 0,
+                             s, (const T *)pred, label, C, sh.HW, units, lse, ws);
+        };
+        if (vec) go(IntTag<4>{}); else go(IntTag<1>{});
+      });
+    });
   } else {
     const bool vec = aligned16(pred) && C % 4 == 0;
     const int gsh = group_shift(vec ? C / 4 : C), ppw = 64 >> gsh;
@@ -609,12 +590,16 @@ extern "C" int m3_loss_ce_fwd(const void *pred, int dtype, const void *label, in
     // the grid is held to the blocks the workspace was sized for (m3_loss_ws_elems) and the kernel's loop takes the rest
     nblk = blocks_for(steps, vec ? 16 : 4);
     if (nblk > blocks_for(sh.n, LS_THREADS)) nblk = blocks_for(sh.n, LS_THREADS);
-    LOSS_BY_DTYPE(dtype, LOSS_BY_LABEL(label_dtype, {
-      if (vec) hipLaunchKernelGGL((ce_fwd_cl4_kernel<T, L>), dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label,
-                                  C, sh.npix, gsh, lse, ws);
-      else hipLaunchKernelGGL((ce_fwd_cl1_kernel<T, L>), dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label, C,
-                              sh.npix, gsh, lse, ws);
-    }));
+    by_dtype(dtype, [&](auto tt) {
+      typedef typename decltype(tt)::type T;
+      by_label(label_dtype, [&](auto lt) {
+        constexpr int L = decltype(lt)::value;
+        // (the 16-byte and the scalar form are two kernels that differ by NAME, not by a template argument a tag could carry:
+        // both have one signature, so the choice is a pointer and the launch is still written once)
+        auto *kern = vec ? ce_fwd_cl4_kernel<T, L> : ce_fwd_cl1_kernel<T, L>;
+        hipLaunchKernelGGL(kern, dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label, C, sh.npix, gsh, lse, ws);
+      });
+    });
   }
   if (int rc = check_launch("m3_loss_ce_fwd (partials)")) return rc;
   return finalize(ws, nblk, K_CE, (double)sh.n, 0, 0.0, record, s, "m3_loss_ce_fwd (finalize)");
@@ -633,22 +618,30 @@ extern "C" int m3_loss_ce_bwd(const void *pred, int dtype, const void *label, in
     const bool vec = aligned16(pred) && aligned16(dpred) && aligned16(lse) && sh.HW % 4 == 0;
     const int units = vec ? sh.npix / 4 : sh.npix;
     const int nblk = blocks_for(units, LS_THREADS);
-    LOSS_BY_DTYPE(dtype, LOSS_BY_LABEL(label_dtype, {
-      if (vec) hipLaunchKernelGGL((ce_bwd_planar_kernel<T, 4, L>), dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label,
-                                  lse, rec, grad_out, C, sh.HW, units, (T *)dpred);
-      else hipLaunchKernelGGL((ce_bwd_planar_kernel<T, 1, L>), dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label,
-                              lse, rec, grad_out, C, sh.HW, units, (T *)dpred);
-    }));
+    by_dtype(dtype, [&](auto tt) {
+      typedef typename decltype(tt)::type T;
+      by_label(label_dtype, [&](auto lt) {
+        auto go = [&](auto v) {
+          hipLaunchKernelGGL((ce_bwd_planar_kernel<T, decltype(v)::value, decltype(lt)::value>), dim3(nblk), dim3(LS_THREADS), 0,
+                             s, (const T *)pred, label, lse, rec, grad_out, C, sh.HW, units, (T *)dpred);
+        };
+        if (vec) go(IntTag<4>{}); else go(IntTag<1>{});
+      });
+    });
   } else {
     const bool vec = aligned16(pred) && aligned16(dpred) && C % 4 == 0;
     const int units = (int)(vec ? sh.n / 4 : sh.n);
     const int nblk = blocks_for(units, LS_THREADS * 2);
-    LOSS_BY_DTYPE(dtype, LOSS_BY_LABEL(label_dtype, {
-      if (vec) hipLaunchKernelGGL((ce_bwd_cl_kernel<T, 4, L>), dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label,
-                                  lse, rec, grad_out, C, units, (T *)dpred);
-      else hipLaunchKernelGGL((ce_bwd_cl_kernel<T, 1, L>), dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label,
-                              lse, rec, grad_out, C, units, (T *)dpred);
-    }));
+    by_dtype(dtype, [&](auto tt) {
+      typedef typename decltype(tt)::type T;
+      by_label(label_dtype, [&](auto lt) {
+        auto go = [&](auto v) {
+          hipLaunchKernelGGL((ce_bwd_cl_kernel<T, decltype(v)::value, decltype(lt)::value>), dim3(nblk), dim3(LS_THREADS), 0, s,
+                             (const T *)pred, label, lse, rec, grad_out, C, units, (T *)dpred);
+        };
+        if (vec) go(IntTag<4>{}); else go(IntTag<1>{});
+      });
+    });
   }
   return check_launch("m3_loss_ce_bwd");
 }
@@ -662,15 +655,14 @@ static int flat_launch(const void *pred, int dtype, const float *label, const vo
   const int units = (int)(vec ? sh.n / 4 : sh.n);
   const int nblk = blocks_for(units, LS_THREADS * 2);
   const float *rec = (const float *)record;
-  LOSS_BY_DTYPE(dtype, {
-    if (bwd && vec) hipLaunchKernelGGL((flat_kernel<T, 4, KIND, true>), dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label,
-                                       rec, grad_out, units, (T *)dpred, ws);
-    else if (bwd) hipLaunchKernelGGL((flat_kernel<T, 1, KIND, true>), dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label,
-                                     rec, grad_out, units, (T *)dpred, ws);
-    else if (vec) hipLaunchKernelGGL((flat_kernel<T, 4, KIND, false>), dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label,
-                                     rec, grad_out, units, (T *)nullptr, ws);
-    else hipLaunchKernelGGL((flat_kernel<T, 1, KIND, false>), dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label, rec,
-                            grad_out, units, (T *)nullptr, ws);
+  by_dtype(dtype, [&](auto tt) {
+    typedef typename decltype(tt)::type T;
+    auto go = [&](auto v, auto b) {
+      hipLaunchKernelGGL((flat_kernel<T, decltype(v)::value, KIND, decltype(b)::value != 0>), dim3(nblk), dim3(LS_THREADS), 0, s,
+                         (const T *)pred, label, rec, grad_out, units, (T *)dpred, ws);
+    };
+    auto with_v = [&](auto v) { if (bwd) go(v, IntTag<1>{}); else go(v, IntTag<0>{}); };
+    if (vec) with_v(IntTag<4>{}); else with_v(IntTag<1>{});
   });
   *nblk_out = nblk;
   return 0;
@@ -727,15 +719,14 @@ static int normals_launch(const void *pred, int dtype, const float *label, const
   const int lsp = label_layout == M3_LAYOUT_NCHW ? 1 : C, lsc = label_layout == M3_LAYOUT_NCHW ? HW : 1;
   const int nblk = blocks_for(sh.npix, LS_THREADS);
   const float *rec = (const float *)record;
-  LOSS_BY_DTYPE(dtype, {
-    if (bwd && C == 3) hipLaunchKernelGGL((normals_kernel<T, 3, true>), dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label,
-                                          rec, grad_out, C, HW, sh.npix, xsp, xsc, lsp, lsc, norm, (T *)dpred, ws);
-    else if (bwd) hipLaunchKernelGGL((normals_kernel<T, 0, true>), dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label, rec,
-                                     grad_out, C, HW, sh.npix, xsp, xsc, lsp, lsc, norm, (T *)dpred, ws);
-    else if (C == 3) hipLaunchKernelGGL((normals_kernel<T, 3, false>), dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label,
-                                        rec, grad_out, C, HW, sh.npix, xsp, xsc, lsp, lsc, norm, (T *)nullptr, ws);
-    else hipLaunchKernelGGL((normals_kernel<T, 0, false>), dim3(nblk), dim3(LS_THREADS), 0, s, (const T *)pred, label, rec,
-                            grad_out, C, HW, sh.npix, xsp, xsc, lsp, lsc, norm, (T *)nullptr, ws);
+  by_dtype(dtype, [&](auto tt) {
+    typedef typename decltype(tt)::type T;
+    auto go = [&](auto ct, auto b) {
+      hipLaunchKernelGGL((normals_kernel<T, decltype(ct)::value, decltype(b)::value != 0>), dim3(nblk), dim3(LS_THREADS), 0, s,
+                         (const T *)pred, label, rec, grad_out, C, HW, sh.npix, xsp, xsc, lsp, lsc, norm, (T *)dpred, ws);
+    };
+    auto with_c = [&](auto ct) { if (bwd) go(ct, IntTag<1>{}); else go(ct, IntTag<0>{}); };
+    if (!by_int<3>(C, with_c)) with_c(IntTag<0>{});
   });
   return nblk;
 }

@@ -18,75 +18,13 @@
 
 namespace m3 {
 
-template <typename T> struct RzVec;                 // one 16-byte vector of T <-> NV fp32 lanes
-template <> struct RzVec<float> {
-  static constexpr int NV = 4;
-  static __device__ __forceinline__ void load(const float *p, float (&v)[4]) {
-    const f32x4 t = *(const f32x4 *)p;
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  }
-  static __device__ __forceinline__ void store(float *p, const float (&v)[4]) { *(f32x4 *)p = f32x4{v[0], v[1], v[2], v[3]}; }
-};
-template <> struct RzVec<half_t> {
-  static constexpr int NV = 8;
-  static __device__ __forceinline__ void load(const half_t *p, float (&v)[8]) {
-    const f16x8 h = *(const f16x8 *)p;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)h[j];
-  }
-  static __device__ __forceinline__ void store(half_t *p, const float (&v)[8]) {
-    f16x8 h;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) h[j] = (half_t)v[j];
-    *(f16x8 *)p = h;
-  }
-};
-template <> struct RzVec<bf16_t> {
-  static constexpr int NV = 8;
-  static __device__ __forceinline__ void load(const bf16_t *p, float (&v)[8]) {
-    const bf16x8 h = *(const bf16x8 *)p;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)h[j];
-  }
-  static __device__ __forceinline__ void store(bf16_t *p, const float (&v)[8]) {
-    bf16x8 h;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) h[j] = (bf16_t)v[j];
-    *(bf16x8 *)p = h;
-  }
-};
-
-// store NV fp32 lanes as TO (NV is the INPUT's vector width: an fp32 output of a 16-bit input takes two 16-byte stores)
-template <typename TO, int NV> __device__ __forceinline__ void rz_store(TO *p, const float (&v)[NV]) {
-  if constexpr (sizeof(TO) == 4 && NV == 8) {
-    *(f32x4 *)p = f32x4{v[0], v[1], v[2], v[3]};
-    *(f32x4 *)(p + 4) = f32x4{v[4], v[5], v[6], v[7]};
-  } else if constexpr (sizeof(TO) == 2 && NV == 4) {
-    typename Vec4<TO>::type h;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) h[j] = (TO)v[j];
-    *(typename Vec4<TO>::type *)p = h;
-  } else {
-    RzVec<TO>::store(p, v);
-  }
-}
-template <typename TG, int NV> __device__ __forceinline__ void rz_load(const TG *p, float (&v)[NV]) {
-  if constexpr (sizeof(TG) == 4 && NV == 8) {
-    const f32x4 a = *(const f32x4 *)p, b = *(const f32x4 *)(p + 4);
-    v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
-  } else if constexpr (sizeof(TG) == 2 && NV == 4) {
-    const typename Vec4<TG>::type h = *(const typename Vec4<TG>::type *)p;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = (float)h[j];
-  } else {
-    RzVec<TG>::load(p, v);
-  }
-}
+constexpr int RZ_BYTES = 16;           // a thread's channels are one 16-byte vector of the INPUT dtype: Pack<T, RZ_BYTES / sizeof(T)>;
+                                       // an fp32 output or gradient of a 16-bit input is the same count, two 16-byte accesses
 
 template <typename T, typename TO, bool RELU>
 __global__ __launch_bounds__(256) void relu_up2x_fwd_kernel(const T *__restrict__ x, int64_t total, int H, int W, int C,
                                                             TO *__restrict__ y) {
-  constexpr int NV = RzVec<T>::NV;
+  constexpr int NV = RZ_BYTES / (int)sizeof(T);
   const int CV = C / NV;
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= total) return;
@@ -104,7 +42,7 @@ __global__ __launch_bounds__(256) void relu_up2x_fwd_kernel(const T *__restrict_
   for (int a = 0; a < 3; ++a)
 #pragma unroll
     for (int b = 0; b < 3; ++b) {
-      RzVec<T>::load(base + ((int64_t)rows[a] * W + cols[b]) * C, z[a][b]);
+      Pack<T, NV>::load(base + ((int64_t)rows[a] * W + cols[b]) * C, z[a][b]);
       if (RELU) {
 #pragma unroll
         for (int j = 0; j < NV; ++j) z[a][b][j] = z[a][b][j] > 0.f ? z[a][b][j] : 0.f;
@@ -129,15 +67,15 @@ __global__ __launch_bounds__(256) void relu_up2x_fwd_kernel(const T *__restrict_
       o0[j] = 0.25f * h[0][b][j] + 0.75f * h[1][b][j];
       o1[j] = 0.75f * h[1][b][j] + 0.25f * h[2][b][j];
     }
-    rz_store<TO, NV>(out + b * C, o0);
-    rz_store<TO, NV>(out + orow + b * C, o1);
+    Pack<TO, NV>::store(out + b * C, o0);
+    Pack<TO, NV>::store(out + orow + b * C, o1);
   }
 }
 
 template <typename T, typename TG, bool RELU>
 __global__ __launch_bounds__(256) void relu_up2x_bwd_kernel(const TG *__restrict__ dy, const T *__restrict__ x, int64_t total,
                                                             int H, int W, int C, T *__restrict__ dx) {
-  constexpr int NV = RzVec<T>::NV;
+  constexpr int NV = RZ_BYTES / (int)sizeof(T);
   const int CV = C / NV;
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= total) return;
@@ -168,7 +106,7 @@ __global__ __launch_bounds__(256) void relu_up2x_bwd_kernel(const TG *__restrict
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
       float g[NV];
-      rz_load<TG, NV>(gbase + ((int64_t)oy[a] * W2 + ox[b]) * C, g);
+      Pack<TG, NV>::load(gbase + ((int64_t)oy[a] * W2 + ox[b]) * C, g);
 #pragma unroll
       for (int j = 0; j < NV; ++j) rowacc[j] += wgt[b] * g[j];
     }
@@ -178,11 +116,11 @@ __global__ __launch_bounds__(256) void relu_up2x_bwd_kernel(const TG *__restrict
   const int64_t off = ((n * H + iy) * (int64_t)W + ix) * C + cv * NV;
   if (RELU) {
     float xv[NV];
-    RzVec<T>::load(x + off, xv);
+    Pack<T, NV>::load(x + off, xv);
 #pragma unroll
     for (int j = 0; j < NV; ++j) acc[j] = xv[j] > 0.f ? acc[j] : 0.f;
   }
-  RzVec<T>::store(dx + off, acc);
+  Pack<T, NV>::store(dx + off, acc);
 }
 
 }  // namespace m3
@@ -194,22 +132,6 @@ static bool rz_shape_ok(int dtype, int64_t N, int H, int W, int C) {
   return N >= 0 && H >= 1 && W >= 1 && C >= nv && C % nv == 0 && N * H * (int64_t)W * C < ((int64_t)1 << 40);
 }
 
-template <typename T, typename TO>
-static void rz_launch_fwd(const void *x, int64_t N, int H, int W, int C, int relu, void *y, hipStream_t s) {
-  const int64_t total = N * H * (int64_t)W * (C / RzVec<T>::NV);
-  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (relu) hipLaunchKernelGGL((relu_up2x_fwd_kernel<T, TO, true>), grid, block, 0, s, (const T *)x, total, H, W, C, (TO *)y);
-  else hipLaunchKernelGGL((relu_up2x_fwd_kernel<T, TO, false>), grid, block, 0, s, (const T *)x, total, H, W, C, (TO *)y);
-}
-
-template <typename T, typename TG>
-static void rz_launch_bwd(const void *dy, const void *x, int64_t N, int H, int W, int C, int relu, void *dx, hipStream_t s) {
-  const int64_t total = N * H * (int64_t)W * (C / RzVec<T>::NV);
-  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (relu) hipLaunchKernelGGL((relu_up2x_bwd_kernel<T, TG, true>), grid, block, 0, s, (const TG *)dy, (const T *)x, total, H, W, C, (T *)dx);
-  else hipLaunchKernelGGL((relu_up2x_bwd_kernel<T, TG, false>), grid, block, 0, s, (const TG *)dy, (const T *)x, total, H, W, C, (T *)dx);
-}
-
 extern "C" int m3_relu_up2x_fwd(const void *x, int x_dtype, int64_t N, int H, int W, int C, int relu, void *y, int y_dtype,
                                 void *stream) {
   M3_REQUIRE(x && y, "m3_relu_up2x_fwd: null operand");
@@ -218,9 +140,18 @@ extern "C" int m3_relu_up2x_fwd(const void *x, int x_dtype, int64_t N, int H, in
   M3_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)y % 16) == 0, "m3_relu_up2x_fwd: 16-byte aligned tensors");
   if (N == 0) return M3_OK;
   hipStream_t s = (hipStream_t)stream;
-  if (x_dtype == M3_F32) rz_launch_fwd<float, float>(x, N, H, W, C, relu, y, s);
-  else if (x_dtype == M3_F16) { if (y_dtype == M3_F32) rz_launch_fwd<half_t, float>(x, N, H, W, C, relu, y, s); else rz_launch_fwd<half_t, half_t>(x, N, H, W, C, relu, y, s); }
-  else { if (y_dtype == M3_F32) rz_launch_fwd<bf16_t, float>(x, N, H, W, C, relu, y, s); else rz_launch_fwd<bf16_t, bf16_t>(x, N, H, W, C, relu, y, s); }
+  by_dtype(x_dtype, [&](auto tt) {
+    typedef typename decltype(tt)::type T;
+    const int64_t total = N * H * (int64_t)W * (C / (RZ_BYTES / (int)sizeof(T)));
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    auto go = [&](auto to, auto r) {
+      typedef typename decltype(to)::type TO;
+      hipLaunchKernelGGL((relu_up2x_fwd_kernel<T, TO, decltype(r)::value != 0>), grid, block, 0, s, (const T *)x, total, H, W, C,
+                         (TO *)y);
+    };
+    auto with_out = [&](auto to) { if (relu) go(to, IntTag<1>{}); else go(to, IntTag<0>{}); };
+    if (y_dtype == M3_F32) with_out(DtypeTag<float>{}); else with_out(tt);
+  });
   return check_launch("m3_relu_up2x_fwd");
 }
 
@@ -232,8 +163,17 @@ extern "C" int m3_relu_up2x_bwd(const void *dy, int dy_dtype, const void *x, int
   M3_REQUIRE(((uintptr_t)dy % 16) == 0 && ((uintptr_t)dx % 16) == 0 && ((uintptr_t)x % 16) == 0, "m3_relu_up2x_bwd: 16-byte aligned tensors");
   if (N == 0) return M3_OK;
   hipStream_t s = (hipStream_t)stream;
-  if (x_dtype == M3_F32) rz_launch_bwd<float, float>(dy, x, N, H, W, C, relu, dx, s);
-  else if (x_dtype == M3_F16) { if (dy_dtype == M3_F32) rz_launch_bwd<half_t, float>(dy, x, N, H, W, C, relu, dx, s); else rz_launch_bwd<half_t, half_t>(dy, x, N, H, W, C, relu, dx, s); }
-  else { if (dy_dtype == M3_F32) rz_launch_bwd<bf16_t, float>(dy, x, N, H, W, C, relu, dx, s); else rz_launch_bwd<bf16_t, bf16_t>(dy, x, N, H, W, C, relu, dx, s); }
+  by_dtype(x_dtype, [&](auto tt) {
+    typedef typename decltype(tt)::type T;
+    const int64_t total = N * H * (int64_t)W * (C / (RZ_BYTES / (int)sizeof(T)));
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    auto go = [&](auto tg, auto r) {
+      typedef typename decltype(tg)::type TG;
+      hipLaunchKernelGGL((relu_up2x_bwd_kernel<T, TG, decltype(r)::value != 0>), grid, block, 0, s, (const TG *)dy, (const T *)x,
+                         total, H, W, C, (T *)dx);
+    };
+    auto with_grad = [&](auto tg) { if (relu) go(tg, IntTag<1>{}); else go(tg, IntTag<0>{}); };
+    if (dy_dtype == M3_F32) with_grad(DtypeTag<float>{}); else with_grad(tt);
+  });
   return check_launch("m3_relu_up2x_bwd");
 }

@@ -3,7 +3,7 @@
 // 540-562) - gate entropy, top-1 probability, the expert load histogram, the clean-logit spread, the MoE output / input
 // norm ratio and the load CV - written as ONE small record in device memory that the host copies only when asked.
 //
-// Stage 1 follows the row-op idiom of rowops.hip: one wave owns one token row at a time (rows are dealt to the waves of a
+// Stage 1 follows the row-kernel idiom of combine.hip: one wave owns one token row at a time (rows are dealt to the waves of a
 // fixed grid in a fixed order), lane e holds expert e of the row's gates / clean logits, the row of h and the k rows of y
 // are read as 16-byte lane vectors that are all issued before the first use, everything accumulates in fp32, and every
 // workgroup leaves one row of partials [nblk][5 + E] in the caller's workspace.  Stage 2 (one workgroup) adds the partials
@@ -23,23 +23,6 @@ static inline int stats_blocks(int64_t T) {
   return (int)(b < 1 ? 1 : (b > ST_MAX_BLOCKS ? ST_MAX_BLOCKS : b));
 }
 
-template <typename T> struct Row16 {                     // one 16-byte lane vector of a row, as floats
-  static constexpr int VE = 16 / (int)sizeof(T);
-};
-
-template <typename T>
-__device__ __forceinline__ void load16(const T *p, float (&v)[16 / sizeof(T)]) {
-  if constexpr (sizeof(T) == 4) {
-    const f32x4 a = *(const f32x4 *)p;
-    v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
-  } else {
-    f32x4 a, b;
-    Vec8<T>::load(p, a, b);
-    v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
-    v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];
-  }
-}
-
 // KT: top-k as a template constant (1, 2, 4, 8; 0 = run-time k), as in combine_fwd_kernel: unrolled, the k row loads of a
 // 16-byte column are in flight together.
 template <typename T, int KT>
@@ -47,7 +30,7 @@ __global__ __launch_bounds__(ST_THREADS) void moe_stats_kernel(const float *__re
                                                                const float *__restrict__ gates, const T *__restrict__ h,
                                                                int64_t ldh, const T *__restrict__ y, int64_t ldy,
                                                                int64_t T_, int E, int k_rt, int D, float *__restrict__ ws) {
-  constexpr int VE = Row16<T>::VE;
+  constexpr int VE = 16 / (int)sizeof(T);               // one 16-byte lane vector of a row, as floats
   const int k = KT ? KT : k_rt;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool valid = lane < E;
@@ -64,11 +47,11 @@ __global__ __launch_bounds__(ST_THREADS) void moe_stats_kernel(const float *__re
       const bool on = col0 < D;
       const int col = on ? col0 : 0;                     // unconditional loads: lanes past D re-read column 0
       float hv[VE], m[VE];
-      load16<T>(h + t * ldh + col, hv);
+      Pack<T, VE>::load(h + t * ldh + col, hv);
       if constexpr (KT > 0) {
         float yv[KT][VE], sv[KT];
 #pragma unroll
-        for (int j = 0; j < KT; ++j) { load16<T>(y + (t * KT + j) * ldy + col, yv[j]); sv[j] = sc[j]; }
+        for (int j = 0; j < KT; ++j) { Pack<T, VE>::load(y + (t * KT + j) * ldy + col, yv[j]); sv[j] = sc[j]; }
 #pragma unroll
         for (int i = 0; i < VE; ++i) m[i] = 0.f;
 #pragma unroll
@@ -80,7 +63,7 @@ __global__ __launch_bounds__(ST_THREADS) void moe_stats_kernel(const float *__re
         for (int i = 0; i < VE; ++i) m[i] = 0.f;
         for (int j = 0; j < k; ++j) {
           float yv[VE];
-          load16<T>(y + (t * k + j) * ldy + col, yv);
+          Pack<T, VE>::load(y + (t * k + j) * ldy + col, yv);
           const float s = sc[j];
 #pragma unroll
           for (int i = 0; i < VE; ++i) m[i] = __builtin_fmaf(s, yv[i], m[i]);
@@ -219,11 +202,14 @@ extern "C" int m3_moe_stats(const float *score, const float *clean, const float 
              "m3_moe_stats: rows of h / y must be 16-byte multiples at 16-byte aligned addresses (D=%d)", D);
   hipStream_t s = (hipStream_t)stream;
   const int nblk = stats_blocks(T);
-#define M3_ST(TT, KT_) hipLaunchKernelGGL((moe_stats_kernel<TT, KT_>), dim3(nblk), dim3(ST_THREADS), 0, s, score, clean, gates, (const TT *)h, ldh, (const TT *)y, ldy, T, E, k, D, ws)
-#define M3_ST_K(TT) do { if (k == 4) M3_ST(TT, 4); else if (k == 2) M3_ST(TT, 2); else if (k == 1) M3_ST(TT, 1); else if (k == 8) M3_ST(TT, 8); else M3_ST(TT, 0); } while (0)
-  if (dtype == M3_F16) M3_ST_K(half_t); else if (dtype == M3_BF16) M3_ST_K(bf16_t); else M3_ST_K(float);
-#undef M3_ST_K
-#undef M3_ST
+  by_dtype(dtype, [&](auto tt) {
+    typedef typename decltype(tt)::type TT;
+    auto go = [&](auto kt) {
+      hipLaunchKernelGGL((moe_stats_kernel<TT, decltype(kt)::value>), dim3(nblk), dim3(ST_THREADS), 0, s, score, clean, gates,
+                         (const TT *)h, ldh, (const TT *)y, ldy, T, E, k, D, ws);
+    };
+    if (!by_int<4, 2, 1, 8>(k, go)) go(IntTag<0>{});
+  });
   int rc = check_launch("m3_moe_stats");
   if (rc != M3_OK) return rc;
   hipLaunchKernelGGL(moe_stats_finish_kernel, dim3(1), dim3(ST_FIN_THREADS), 0, s, (const float *)ws, nblk, E, T, load_f32,

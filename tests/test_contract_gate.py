@@ -400,6 +400,12 @@ PARAM_CASES = [
     (F16, 256, 24, 0, "fallback E>16"), (F32, 100, 48, 0, "fallback ep64"), (BF16, 102, 16, 0, "fallback D%4"),
     (F16, 256, 16, 1, "fallback ldx breaks 8B"), (F32, 64, 64, 0, "fallback ep64 E64"), (F32, 130, 32, 0, "fallback ep32"),
     (BF16, 96, 12, 0, "dw4 ep16 padded E"), (F16, 48, 5, 0, "dw4 ep8 padded E"),
+    # the remaining (dtype, padded E) pairs of both dW kernels: D = 132 takes the four-wide kernel, D = 130 (no multiple of 4)
+    # the fallback
+    (F32, 132, 16, 0, "dw4 f32 ep16"),
+    (F16, 130, 8, 0, "fallback f16 ep8"), (F16, 130, 64, 0, "fallback f16 ep64"), (BF16, 130, 8, 0, "fallback bf16 ep8"),
+    (BF16, 130, 32, 0, "fallback bf16 ep32"), (BF16, 130, 64, 0, "fallback bf16 ep64"), (F32, 130, 8, 0, "fallback f32 ep8"),
+    (F32, 130, 16, 0, "fallback f32 ep16"),
 ]
 
 

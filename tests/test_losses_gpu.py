@@ -218,6 +218,34 @@ def test_integer_class_labels(layout, label_dtype):
         check("ce", x, lab, None, c, what="int64 bad labels")
 
 
+@pytest.mark.parametrize("dtype", LC.DTYPES, ids=_dt)
+@pytest.mark.parametrize("label_dtype", [torch.int64, torch.uint8], ids=_dt)
+@pytest.mark.parametrize("layout", LC.LAYOUTS)
+def test_integer_class_labels_on_the_vector_paths(layout, label_dtype, dtype):
+    """C = 20 and H * W = 528, both multiples of 4: the 16-byte kernels of either layout (the planar pair, ce_fwd_cl4, the
+    vector ce_bwd_cl) with int64 and uint8 labels in every pred dtype - the same bits as with float labels"""
+    pred, label = LC.make_inputs("ce", 20, (3, 16, 33))
+    x = place(pred, dtype, layout)
+    a = run("ce", x, label, label_dtype=label_dtype)
+    check("ce", x, label, None, a, what=f"vector ce {layout} {_dt(label_dtype)} {_dt(dtype)}")
+    b = run("ce", x, label)
+    assert torch.equal(a["record"], b["record"]) and same_bits(a["grad"], b["grad"]) and same_bits(a["lse"], b["lse"])
+
+
+@pytest.mark.parametrize("dtype", LC.DTYPES, ids=_dt)
+@pytest.mark.parametrize("layout", LC.LAYOUTS)
+@pytest.mark.parametrize("case", [("l1", 1, (3, 16, 33), None), ("bce", 1, (3, 16, 33), None), ("bce", 1, (3, 16, 33), 0.95),
+                                  ("normals", 2, (3, 17, 33), 1), ("normals", 5, (3, 17, 33), 2), ("normals", 8, (2, 3, 7), 1)],
+                         ids=LC.case_id)
+def test_flat_vector_path_and_run_time_channel_count(case, layout, dtype):
+    """the 16-byte path of the flat losses in every dtype (1584 elements: whole vectors, aligned storage), and the normals
+    kernel with C as a run-time value (every C but 3), up to the largest it takes"""
+    kind, C, size, extra = case
+    pred, label = LC.make_inputs(kind, C, size)
+    x = place(pred, dtype, layout)
+    check(kind, x, label, extra, run(kind, x, label, extra), what=f"{LC.case_id(case)} {layout} {_dt(dtype)}")
+
+
 # ------------------------------------------------------------------------------------------------ upstream gradients
 def _module(kind, extra):
     from m3vit_amd import losses
