@@ -680,6 +680,73 @@ int m3_loss_bce_fwd(const void *pred, int dtype, const float *label, int B, int 
 int m3_loss_bce_bwd(const void *pred, int dtype, const float *label, const void *record, const float *grad_out, int B, int C,
                     int H, int W, int layout, void *dpred, void *stream);
 
+/* ------------------------------------------------------------- task metrics
+ * What the reference's PerformanceMeter accumulates after every forward (evaluation/eval_semseg.py:109-120,
+ * eval_human_parts.py:88-98, eval_depth.py:67-85, eval_normals.py:72-94, eval_sal.py:75-96 with jaccard.py), from the RAW head
+ * output: utils/utils.py:60-79 (get_output: argmax, normalise, sigmoid) is fused in, nothing of pred's size is written.  An
+ * update is two launches - per-workgroup partials, then one workgroup that adds them in block order (float sums in double)
+ * INTO `state`.  No global atomics, nothing read back to the host, the same bits from run to run.
+ *
+ * pred, dtype, layout, label_dtype, the 16-byte / scalar access rule and the size limit: as for the losses above.  Label 255 is
+ * "ignore" for every meter but saliency.
+ * ws: m3_meter_ws_elems(kind, B*C*H*W, aux) four-byte words, no initialisation; aux: n_classes (M3_METER_IOU), B
+ * (M3_METER_SAL), ignored otherwise.  0 for arguments the update would refuse.
+ * state: 8-byte words the update ADDS to (int64 counts, double sums); the caller zeroes them (a memset) to reset, and may sum
+ * the states of several processes.  Layouts, as word indices:
+ *   IoU      [M3_METER_IOU_WORDS]: int64 [3][M3_METER_IOU_BINS] at M3_METER_IOU_TP (label == prediction == i),
+ *            M3_METER_IOU_PRED (prediction == i) and M3_METER_IOU_LABEL (label == i), over the pixels with label != 255; bins
+ *            [0, n_classes) are written.  fp = PRED - TP, fn = LABEL - TP.
+ *   depth    [M3_METER_DEPTH_WORDS]: f64 SUM_SQ, f64 SUM_LOG_SQ, i64 N_VALID
+ *   normals  [M3_METER_NORMALS_WORDS]: f64 SUM_ANGLE, f64 SUM_SQ (degrees, degrees^2), i64 N_11 / N_22 / N_30 (angles below
+ *            11.25 / 22.5 / 30 degrees), i64 N
+ *   saliency [M3_METER_SAL_WORDS]: f64 [3][M3_METER_SAL_THRESHOLDS] at M3_METER_SAL_JACCARD / _PREC / _REC: per-image values
+ *            summed over the images; i64 N_IMAGES
+ *
+ * IoU: prediction = argmax over C, lowest index on ties, a NaN beats everything and the first NaN wins (torch.max); C in
+ *   [2, 255], n_classes in [1, 256].  A float label is class i only where it EQUALS i; a valid label that is no class in
+ *   [0, n_classes) matches none and still counts its pixel in PRED.
+ * depth: over label != 255: (label - p)^2 and (log label - log p)^2 with p = max(pred, 1e-9); label f32 in pred's layout.
+ * normals (C = 3): t = pred / max(|pred|_2, 1e-12); elements with label == 255 are zeroed in t and label; angle =
+ *   (180 / pi) acos(clamp(sum_c t label, -1, 1)); a pixel counts where channel 0 of its label is valid.
+ * saliency (C = 1, B <= M3_LOSS_MAX_BLOCKS): p = sigmoid(pred) in fp32 against the fp32 values of linspace(0.2, 0.9, 15), label
+ *   != 0; per image and threshold jaccard (1 when both masks are empty), tp / (tp + fp + 1e-12) and tp / (tp + fn + 1e-12) in
+ *   double from exact counts. */
+#define M3_METER_IOU 0
+#define M3_METER_DEPTH 1
+#define M3_METER_NORMALS 2
+#define M3_METER_SAL 3
+#define M3_METER_IOU_BINS 256
+#define M3_METER_IOU_TP 0
+#define M3_METER_IOU_PRED 256
+#define M3_METER_IOU_LABEL 512
+#define M3_METER_IOU_WORDS 768
+#define M3_METER_DEPTH_SUM_SQ 0
+#define M3_METER_DEPTH_SUM_LOG_SQ 1
+#define M3_METER_DEPTH_N_VALID 2
+#define M3_METER_DEPTH_WORDS 4
+#define M3_METER_NORMALS_SUM_ANGLE 0
+#define M3_METER_NORMALS_SUM_SQ 1
+#define M3_METER_NORMALS_N_11 2
+#define M3_METER_NORMALS_N_22 3
+#define M3_METER_NORMALS_N_30 4
+#define M3_METER_NORMALS_N 5
+#define M3_METER_NORMALS_WORDS 8
+#define M3_METER_SAL_THRESHOLDS 15
+#define M3_METER_SAL_JACCARD 0
+#define M3_METER_SAL_PREC 15
+#define M3_METER_SAL_REC 30
+#define M3_METER_SAL_N_IMAGES 45
+#define M3_METER_SAL_WORDS 48
+int64_t m3_meter_ws_elems(int kind, int64_t n, int aux);
+int m3_meter_iou_update(const void *pred, int dtype, const void *label, int label_dtype, int B, int C, int H, int W, int layout,
+                        int n_classes, void *ws, void *state, void *stream);
+int m3_meter_depth_update(const void *pred, int dtype, const float *label, int B, int C, int H, int W, int layout, void *ws,
+                          void *state, void *stream);
+int m3_meter_normals_update(const void *pred, int dtype, const float *label, int B, int H, int W, int layout, int label_layout,
+                            void *ws, void *state, void *stream);
+int m3_meter_sal_update(const void *pred, int dtype, const float *label, int B, int H, int W, void *ws, void *state,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

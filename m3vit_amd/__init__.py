@@ -24,11 +24,17 @@ def install_fmoe_shim():
 
 _LOSS_NAMES = ("SoftMaxwithLoss", "BalancedCrossEntropyLoss", "DepthLoss", "NormalsLoss", "SingleTaskLoss", "MultiTaskLoss",
                "get_loss")
+_METER_NAMES = ("PerformanceMeter", "SemsegMeter", "HumanPartsMeter", "DepthMeter", "NormalsMeter", "SaliencyMeter", "EdgeMeter",
+                "AverageMeter", "get_single_task_meter", "calculate_multi_task_performance", "get_output")
 
 
 def __getattr__(name):
-    """the criterion modules of m3vit_amd.losses, importable from the package (loaded on first use: they need torch)"""
+    """the criterion modules of m3vit_amd.losses and the task meters of m3vit_amd.meters, importable from the package (loaded
+    on first use: they need torch)"""
     if name in _LOSS_NAMES:
         from . import losses
         return getattr(losses, name)
+    if name in _METER_NAMES:
+        from . import meters
+        return getattr(meters, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -21,6 +21,13 @@ M3_LABEL_F32, M3_LABEL_I64, M3_LABEL_U8 = 0, 1, 2
 M3_LOSS_MAX_BLOCKS, M3_LOSS_NORMALS_MAX_C, M3_LOSS_REC_WORDS = 1024, 8, 8
 (M3_LOSS_REC_VALUE, M3_LOSS_REC_COEF, M3_LOSS_REC_COEF2, M3_LOSS_REC_N_VALID, M3_LOSS_REC_N_AUX,
  M3_LOSS_REC_N_BAD) = range(6)
+M3_METER_IOU, M3_METER_DEPTH, M3_METER_NORMALS, M3_METER_SAL = range(4)
+M3_METER_IOU_BINS, M3_METER_IOU_TP, M3_METER_IOU_PRED, M3_METER_IOU_LABEL, M3_METER_IOU_WORDS = 256, 0, 256, 512, 768
+M3_METER_DEPTH_SUM_SQ, M3_METER_DEPTH_SUM_LOG_SQ, M3_METER_DEPTH_N_VALID, M3_METER_DEPTH_WORDS = 0, 1, 2, 4
+(M3_METER_NORMALS_SUM_ANGLE, M3_METER_NORMALS_SUM_SQ, M3_METER_NORMALS_N_11, M3_METER_NORMALS_N_22, M3_METER_NORMALS_N_30,
+ M3_METER_NORMALS_N, M3_METER_NORMALS_WORDS) = 0, 1, 2, 3, 4, 5, 8
+(M3_METER_SAL_THRESHOLDS, M3_METER_SAL_JACCARD, M3_METER_SAL_PREC, M3_METER_SAL_REC, M3_METER_SAL_N_IMAGES,
+ M3_METER_SAL_WORDS) = 15, 0, 15, 30, 45, 48
 
 
 class M3Error(RuntimeError):
@@ -214,6 +221,11 @@ SIGNATURES = {
     "m3_loss_normals_bwd": (c_int, [_V, _I, _V, _V, _V, _I, _I, _I, _I, _I, _I, _I, _V, _V]),
     "m3_loss_bce_fwd": (c_int, [_V, _I, _V, _I, _I, _I, _I, _I, _I, c_double, _V, _V, _V]),
     "m3_loss_bce_bwd": (c_int, [_V, _I, _V, _V, _V, _I, _I, _I, _I, _I, _V, _V]),
+    "m3_meter_ws_elems": (c_int64, [_I, _L, _I]),
+    "m3_meter_iou_update": (c_int, [_V, _I, _V, _I, _I, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "m3_meter_depth_update": (c_int, [_V, _I, _V, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "m3_meter_normals_update": (c_int, [_V, _I, _V, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "m3_meter_sal_update": (c_int, [_V, _I, _V, _I, _I, _I, _V, _V, _V]),
     "m3_cast_f32": (c_int, [_V, _L, _V, _I, _V]),
     "m3_scale_rows_cast": (c_int, [_V, _L, _I, _V, _I, _V, _I, _V]),
     "m3_im2row": (c_int, [_V, _I, _I, _I, _I, _I, _V, _I, _V]),

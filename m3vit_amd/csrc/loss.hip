@@ -11,13 +11,10 @@
 // Layouts: NCHW-contiguous (lanes run along the pixels of a plane, a loop over C) and channels-last (a pixel's C values are
 // contiguous: a group of G = 2^k lanes reads one pixel as one span, 64 / G pixels of a wave are one contiguous span, and the
 // group reduces with shuffles).  V = 4 elements per access where the host found 16-byte alignment and whole vectors, else V = 1.
-#include "common.h"
-#include <math.h>
+#include "loss_dev.h"
 
 namespace m3 {
 
-constexpr int LS_THREADS = 256;
-constexpr int LS_MAX_BLOCKS = M3_LOSS_MAX_BLOCKS;   // 4 workgroups per CU; with two pieces per thread the bytes in flight of 8 per CU
 constexpr int LS_NP = 4;                            // partial rows: sum0, sum1, count0, count1 - each [nblk]
 constexpr int LS_CCHUNK = 8;                        // channels of a planar pixel in flight together
 
@@ -38,12 +35,6 @@ __device__ __forceinline__ int class_label(const void *__restrict__ lab, int i) 
     const float f = ((const float *)lab)[i];
     return (f > -1.f && f < 256.f) ? (int)f : -1;
   }
-}
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // a workgroup's four partials: wave sums, then the four waves in order
@@ -266,9 +257,7 @@ __global__ __launch_bounds__(LS_THREADS) void ce_fwd_cl1_kernel(const T *__restr
 // permutes, then the half-row and row mirrors: full-rate VALU, every lane of the group ends with the same bits), only groups of
 // 32 and 64 lanes fall back to a shuffle; x[label] is not reduced at all - the lane that holds the label's chunk adds the
 // pixel's term; every level runs over the U steps together; and the next pass's loads are issued before this one is reduced.
-template <int CTRL> __device__ __forceinline__ float dpp_f(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
+template <int CTRL> __device__ __forceinline__ float dpp_f(float v) { return __int_as_float(dpp_i<CTRL>(__float_as_int(v))); }
 template <bool MAX> __device__ __forceinline__ float red2(float a, float b) { return MAX ? fmaxf(a, b) : a + b; }
 
 template <bool MAX, int U>
@@ -513,40 +502,10 @@ __global__ __launch_bounds__(LS_THREADS) void normals_kernel(const T *__restrict
   if (!BWD) block_partials(acc, 0.f, nv, 0, ws);
 }
 
-static inline int blocks_for(int64_t units, int per_block) {
-  const int64_t b = (units + per_block - 1) / per_block;
-  return (int)(b < 1 ? 1 : (b > LS_MAX_BLOCKS ? LS_MAX_BLOCKS : b));
-}
-static inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-struct LossShape { int B, C, H, W, HW, npix; int64_t n; };
-
-static int shape_ok(int B, int C, int H, int W, int cmin, int cmax, int layout, int dtype, const char *who, LossShape *s) {
-  M3_REQUIRE(B >= 1 && H >= 1 && W >= 1, "%s: B, H, W must be positive (got %d, %d, %d)", who, B, H, W);
-  M3_REQUIRE(C >= cmin && C <= cmax, "%s: C = %d outside [%d, %d]", who, C, cmin, cmax);
-  M3_REQUIRE(layout == M3_LAYOUT_NCHW || layout == M3_LAYOUT_NHWC, "%s: bad layout code %d", who, layout);
-  M3_REQUIRE(dtype_ok(dtype), "%s: bad dtype code %d", who, dtype);
-  const int64_t n = (int64_t)B * C * H * W;
-  M3_REQUIRE(n < ((int64_t)1 << 31) - ((int64_t)1 << 20), "%s: %lld elements: the kernels index with 32 bits", who, (long long)n);
-  s->B = B; s->C = C; s->H = H; s->W = W; s->HW = H * W; s->npix = B * H * W; s->n = n;
-  return 0;
-}
-
 static int finalize(const float *ws, int nblk, int kind, double numel, int has_pw, double pw, void *rec, hipStream_t s,
                     const char *who) {
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, s, ws, nblk, kind, numel, has_pw, pw, (int32_t *)rec);
   return check_launch(who);
-}
-
-// f(IntTag<L>{}), L the label dtype code that label_dtype_ok() has accepted
-template <typename F> static inline void by_label(int ldt, F &&f) {
-  if (!by_int<M3_LABEL_I64, M3_LABEL_U8>(ldt, f)) f(IntTag<M3_LABEL_F32>{});
-}
-
-static inline int group_shift(int nch) {                 // lanes per channels-last pixel: the power of two >= nch, at most 64
-  int sh = 0;
-  while ((1 << sh) < nch && sh < 6) ++sh;
-  return sh;
 }
 
 }  // namespace m3
@@ -557,8 +516,6 @@ extern "C" int64_t m3_loss_ws_elems(int64_t n) {
   if (n < 1) return 0;
   return (int64_t)LS_NP * blocks_for(n, LS_THREADS);
 }
-
-static int label_dtype_ok(int ldt) { return ldt == M3_LABEL_F32 || ldt == M3_LABEL_I64 || ldt == M3_LABEL_U8; }
 
 extern "C" int m3_loss_ce_fwd(const void *pred, int dtype, const void *label, int label_dtype, int B, int C, int H, int W,
                               int layout, float *lse, float *ws, void *record, void *stream) {

@@ -1180,6 +1180,92 @@ def loss_bce_bwd(pred, label, record, grad_out, *, dpred=None):
     return dpred
 
 
+# --------------------------------------------------------------------------------------- task metrics (csrc/meter.hip)
+METER_WORDS = {_lib.M3_METER_IOU: _lib.M3_METER_IOU_WORDS, _lib.M3_METER_DEPTH: _lib.M3_METER_DEPTH_WORDS,
+               _lib.M3_METER_NORMALS: _lib.M3_METER_NORMALS_WORDS, _lib.M3_METER_SAL: _lib.M3_METER_SAL_WORDS}
+
+
+def meter_ws_elems(kind: int, n: int, aux: int = 0) -> int:
+    """four-byte words of the partials workspace of a meter update over a pred of n elements (m3_meter_ws_elems); aux:
+    n_classes for the IoU meter, B for saliency"""
+    return int(lib().m3_meter_ws_elems(kind, n, aux))
+
+
+def meter_state(kind: int, device) -> torch.Tensor:
+    """a zeroed accumulator state: int64 words, the double sums among them read through .view(torch.float64)
+    (layout: include/m3vit_hip.h, M3_METER_*)"""
+    return torch.zeros(METER_WORDS[kind], dtype=torch.int64, device=device)
+
+
+def _meter_bufs(kind, pred, aux, ws, state):
+    need = meter_ws_elems(kind, pred.numel(), aux)
+    if need <= 0:
+        raise _lib.M3Error(f"no meter of kind {kind} takes a pred of shape {tuple(pred.shape)} (aux {aux})")
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.int32, device=pred.device)
+    _req(ws, torch.int32, "ws", min_numel=need)
+    if state is None:
+        state = meter_state(kind, pred.device)
+    _req(state, torch.int64, "state", numel=METER_WORDS[kind])
+    return ws, state
+
+
+def meter_iou_update(pred, label, n_classes, *, ws=None, state=None):
+    """Class-IoU counts (m3_meter_iou_update) ADDED to state: pred [B,C,H,W] raw logits (argmax fused in), label [B,1,H,W] or
+    [B,H,W] float32 / int64 / uint8, 255 = ignored.  Returns state.  Nothing is read back."""
+    pred, layout = loss_layout(pred)
+    B, C, H, W = pred.shape
+    _class_label(label, pred)
+    if not 1 <= int(n_classes) <= _lib.M3_METER_IOU_BINS:
+        raise _lib.M3Error(f"n_classes must be in [1, {_lib.M3_METER_IOU_BINS}], got {n_classes}")
+    ws, state = _meter_bufs(_lib.M3_METER_IOU, pred, int(n_classes), ws, state)
+    check(lib().m3_meter_iou_update(_p(pred), dt_code(pred.dtype), _p(label), _LABEL_DT[label.dtype], B, C, H, W, layout,
+                                    int(n_classes), _p(ws), _p(state), _stream()), "m3_meter_iou_update")
+    return state
+
+
+def meter_depth_update(pred, label, *, ws=None, state=None):
+    """Depth sums (m3_meter_depth_update) ADDED to state: over label != 255, (label - p)^2 and (log label - log p)^2 with
+    p = max(pred, 1e-9).  label: float32 of pred's shape.  Returns state."""
+    pred, layout = loss_layout(pred)
+    B, C, H, W = pred.shape
+    label = loss_label_like(label, pred, layout)
+    ws, state = _meter_bufs(_lib.M3_METER_DEPTH, pred, 0, ws, state)
+    check(lib().m3_meter_depth_update(_p(pred), dt_code(pred.dtype), _p(label), B, C, H, W, layout, _p(ws), _p(state), _stream()),
+          "m3_meter_depth_update")
+    return state
+
+
+def meter_normals_update(pred, label, *, ws=None, state=None):
+    """Angular-error sums and counts (m3_meter_normals_update) ADDED to state: pred [B,3,H,W] raw (normalised in the kernel),
+    label float32 [B,3,H,W], each in either layout.  Returns state."""
+    pred, layout = loss_layout(pred)
+    B, C, H, W = pred.shape
+    if C != 3:
+        raise _lib.M3Error(f"the normals meter takes C = 3, got {C}")
+    label, ll = _normals_label(label, pred)
+    ws, state = _meter_bufs(_lib.M3_METER_NORMALS, pred, 0, ws, state)
+    check(lib().m3_meter_normals_update(_p(pred), dt_code(pred.dtype), _p(label), B, H, W, layout, ll, _p(ws), _p(state),
+                                        _stream()), "m3_meter_normals_update")
+    return state
+
+
+def meter_sal_update(pred, label, *, ws=None, state=None):
+    """Saliency (m3_meter_sal_update): per image and threshold jaccard / precision / recall of sigmoid(pred) > t against
+    label != 0, ADDED to state's running sums.  pred [B,1,H,W] raw logits, label float32 of pred's shape.  Returns state."""
+    pred, layout = loss_layout(pred)
+    B, C, H, W = pred.shape
+    if C != 1:
+        raise _lib.M3Error(f"the saliency meter takes C = 1, got {C}")
+    if B > _lib.M3_LOSS_MAX_BLOCKS:
+        raise _lib.M3Error(f"the saliency meter takes at most {_lib.M3_LOSS_MAX_BLOCKS} images per update, got {B}")
+    label = loss_label_like(label, pred, layout)
+    ws, state = _meter_bufs(_lib.M3_METER_SAL, pred, B, ws, state)
+    check(lib().m3_meter_sal_update(_p(pred), dt_code(pred.dtype), _p(label), B, H, W, _p(ws), _p(state), _stream()),
+          "m3_meter_sal_update")
+    return state
+
+
 def cast_f32(src, dst):
     _req(src, torch.float32, "src"); _act(dst, "dst", src.numel())
     check(lib().m3_cast_f32(_p(src), src.numel(), _p(dst), dt_code(dst.dtype), _stream()), "m3_cast_f32")
