@@ -246,6 +246,30 @@ int m3_gemm_nt(const m3_gemm_args *args, void *stream);
  * with streamed operands: K >= 2048 and at least 96 tiles; -1 re-reads M3_GEMM_BIG from the environment.  Results are the same up to fp32
  * summation order either way. */
 int m3_gemm_set_big(int mode);
+/* What m3_gemm_nt would do with `args` under the current m3_gemm_set_big mode and the M3_GEMM_* environment switches, without
+ * doing it: host code shared with the launch (the same checks and error codes, the same kernel choice and tile order), no
+ * GPU work, no operand pointer is read - a test can plan a call on a machine without a GPU from aligned non-NULL dummies.
+ * kernel: which of the four kernels takes the call (M3_GEMM_NONE for M = 0, which launches nothing); epilogue: the kind the
+ * two LDS-DMA kernels are instantiated for (M3_GEMM_EPI_*; the register-staged kernels only have M3_GEMM_EPI_ANY, the
+ * run-time-flag epilogue); tile_m x tile_n: the output tile; m_band: row tiles per band of the tile order; vec8: N and
+ * every leading dimension of C-shaped operands a multiple of 8; n_tiles: column tiles; m_tiles_max: the grid's row tiles
+ * (a grouped call: the upper bound, one partial tile per group). */
+#define M3_GEMM_NONE (-1)
+#define M3_GEMM_STAGED 0         /* csrc/gemm_staged.hip, 128-row tiles */
+#define M3_GEMM_STAGED_TALL 1    /* the same with 160-row tiles (fp32, dense, whole K slices) */
+#define M3_GEMM_DMA 2            /* csrc/gemm_dma.hip */
+#define M3_GEMM_BIG 3            /* csrc/gemm_big.hip, 256 x 256 tiles */
+#define M3_GEMM_EPI_ANY 0        /* every option behind a run-time flag */
+#define M3_GEMM_EPI_GPRE 1       /* * gelu'(gelu_grad_pre), act-dtype C, no bias / residual */
+#define M3_GEMM_EPI_RES 2        /* (+ bias) (* row_scale) + residual, fp32 C */
+#define M3_GEMM_EPI_PLAIN 3      /* (+ bias) (* row_scale), act-dtype C */
+#define M3_GEMM_EPI_GELU 4       /* (+ bias), pre_out, GELU, act-dtype C */
+typedef struct {
+  int32_t kernel, epilogue;
+  int32_t tile_m, tile_n, m_band, vec8;
+  int32_t n_tiles, m_tiles_max;
+} m3_gemm_plan_out;
+int m3_gemm_plan(const m3_gemm_args *args, m3_gemm_plan_out *plan);
 
 /* Weight gradient ("TN", contraction over rows):
  *   dW[g][n, k] (+)= sum_{m in group g} dC[crow(m), n] * A[arow(m), k]
@@ -391,6 +415,22 @@ int m3_wgrad_tile(int N, int K, int dtype, int *tn, int *tk);
  * a 128 x 128 MFMA tile padded eightfold: m3_wgrad_plan then sizes `splits` for a stream over dC.  Slab layout and reduction
  * are unchanged.  The rule is fixed: it depends on the shape only. */
 int m3_wgrad_skinny(int N, int K, int G);
+/* The kernel m3_wgrad_tn would launch for `args` under the current m3_wgrad_set_dma / m3_wgrad_set_big settings, after the
+ * step-downs a call can force (a gather divisor that is no power of two, a per-row factor the family lacks for the dtype or
+ * on rows that are not gathered, operands past the 4 GiB reach: 256 x 256 and the streaming kernel -> a 128 x 128 kernel,
+ * LDS-DMA -> register-staged), and the template instance: gathered dC rows, gathered A rows, per-row factor.  Host code
+ * shared with the launch (the same checks of the call and error codes), no GPU work, no operand pointer is read; the
+ * descriptors behind args->prev are not looked at (they do not enter the choice; the launch checks them). */
+#define M3_WGRAD_KERNEL_STAGED 0   /* csrc/wgrad_staged.hip */
+#define M3_WGRAD_KERNEL_DMA 1      /* csrc/wgrad_dma.hip, 128 x 128 */
+#define M3_WGRAD_KERNEL_BIG 2      /* csrc/wgrad_dma.hip, 256 x 256 */
+#define M3_WGRAD_KERNEL_SKINNY 3   /* csrc/wgrad.hip, the streaming kernel for K = 16 / 32 */
+typedef struct {
+  int32_t kernel;
+  int32_t gather_c, gather_a, scale_c;
+  int32_t tile_n, tile_k;
+} m3_wgrad_kernel_out;
+int m3_wgrad_kernel(const m3_wgrad_args *args, m3_wgrad_kernel_out *out);
 /* balanced mode: dW[g] (+)= sum over group g's units of ws[u] (elems = N*K per group), unit order; optionally the
  * same for the bias slabs (bias_elems = N per group) */
 int m3_wgrad_reduce_grouped(const float *ws, const int32_t *group_offsets, int G, int chunk_rows, int64_t elems,
@@ -511,6 +551,19 @@ int64_t m3_attention_bwd_ws_elems(int B, int N, int heads, int dh);
 int m3_attention_bwd(const void *qkv, const void *o, const void *d_o, const float *lse,
                      int dtype, int B, int N, int heads, int dh, void *dqkv, float *dq_ws,
                      void *stream);
+/* Which kernels m3_attention_fwd / m3_attention_bwd launch for (dtype, N, dh): host code shared with the two entry points
+ * and with the launchers' instance choice, no GPU work.  Family: exact fp32 (any N), the LDS-resident 16-bit kernels
+ * (N <= 256) or the streamed 16-bit ones.  fwd_key_tiles: the key-tile count the resident forward is instantiated for (16-key
+ * tiles rounded up to 4, 8, 12, 16; keys >= N are masked); bwd_tiles_per_wave: the resident backward's instance (dh 32: 1..4,
+ * dh 64: 1..2); both 0 for the other families.  bwd_key_blocks: 256-key blocks of the backward (> 1: dQ slabs + reduction). */
+#define M3_ATTN_F32 0
+#define M3_ATTN_RESIDENT 1
+#define M3_ATTN_STREAMED 2
+typedef struct {
+  int32_t fwd_family, fwd_key_tiles;
+  int32_t bwd_family, bwd_tiles_per_wave, bwd_key_blocks;
+} m3_attention_plan_out;
+int m3_attention_plan(int dtype, int N, int dh, m3_attention_plan_out *plan);
 
 /* ------------------------------------------------------------- elementwise
  * cast / transpose helpers for parameters (fp32 master -> act dtype operand copies):

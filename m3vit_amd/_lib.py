@@ -14,6 +14,10 @@ LIB_PATH = os.environ.get("M3VIT_LIB") or os.path.join(_HERE, "libm3vit_hip.so")
 
 M3_F32, M3_F16, M3_BF16 = 0, 1, 2
 M3_ACT_NONE, M3_ACT_GELU = 0, 1
+GEMM_KERNELS = {-1: "none", 0: "staged", 1: "staged_tall", 2: "dma", 3: "big"}              # M3_GEMM_*
+GEMM_EPILOGUES = {0: "any", 1: "gpre", 2: "res", 3: "plain", 4: "gelu"}                     # M3_GEMM_EPI_*
+WGRAD_KERNELS = {0: "staged", 1: "dma", 2: "big", 3: "skinny"}                              # M3_WGRAD_KERNEL_*
+ATTN_FAMILIES = {0: "f32", 1: "resident", 2: "streamed"}                                    # M3_ATTN_*
 M3_OPTIM_ADAMW, M3_OPTIM_ADAM, M3_OPTIM_SGD = 0, 1, 2
 M3_OPTIM_CHUNK, M3_OPTIM_HYPER, M3_OPTIM_DECOUPLED, M3_OPTIM_NESTEROV = 4096, 8, 1, 2
 M3_LAYOUT_NCHW, M3_LAYOUT_NHWC = 0, 1
@@ -56,6 +60,11 @@ class GemmArgs(Structure):
     ]
 
 
+class GemmPlan(Structure):
+    _fields_ = [("kernel", c_int32), ("epilogue", c_int32), ("tile_m", c_int32), ("tile_n", c_int32), ("m_band", c_int32),
+                ("vec8", c_int32), ("n_tiles", c_int32), ("m_tiles_max", c_int32)]
+
+
 class WgradReduceDesc(Structure):
     _fields_ = [
         ("ws", c_void_p), ("splits", c_int32), ("elems", c_int64),
@@ -81,6 +90,16 @@ class WgradArgs(Structure):
         ("direct_dW", c_void_p), ("direct_db", c_void_p), ("direct_beta", c_int32), ("direct_beta_db", c_int32),
         ("n_prev", c_int32),
     ]
+
+
+class WgradKernelOut(Structure):
+    _fields_ = [("kernel", c_int32), ("gather_c", c_int32), ("gather_a", c_int32), ("scale_c", c_int32),
+                ("tile_n", c_int32), ("tile_k", c_int32)]
+
+
+class AttentionPlan(Structure):
+    _fields_ = [("fwd_family", c_int32), ("fwd_key_tiles", c_int32), ("bwd_family", c_int32), ("bwd_tiles_per_wave", c_int32),
+                ("bwd_key_blocks", c_int32)]
 
 
 class WgradShape(Structure):
@@ -179,6 +198,7 @@ SIGNATURES = {
     "m3_ep_return": (c_int, [_I, _V, _V, _V, _V, _L, _V]),
     "m3_gemm_nt": (c_int, [POINTER(GemmArgs), _V]),
     "m3_gemm_set_big": (c_int, [_I]),
+    "m3_gemm_plan": (c_int, [POINTER(GemmArgs), POINTER(GemmPlan)]),
     "m3_wgrad_tn": (c_int, [POINTER(WgradArgs), _V]),
     "m3_wgrad_plan": (c_int, [POINTER(WgradShape), POINTER(WgradPlan)]),
     "m3_wgrad_multi_plan": (c_int, [POINTER(WgradMultiShape), POINTER(WgradMultiPlan)]),
@@ -186,6 +206,7 @@ SIGNATURES = {
     "m3_wgrad_reduce_multi": (c_int, [POINTER(WgradReduceDesc), _I, _V]),
     "m3_wgrad_tile": (c_int, [_I, _I, _I, POINTER(c_int), POINTER(c_int)]),
     "m3_wgrad_skinny": (c_int, [_I, _I, _I]),
+    "m3_wgrad_kernel": (c_int, [POINTER(WgradArgs), POINTER(WgradKernelOut)]),
     "m3_wgrad_set_dma": (c_int, [_I]),
     "m3_wgrad_set_big": (c_int, [_I]),
     "m3_wgrad_reduce": (c_int, [_V, _I, _L, _V, _I, _V, _L, _V, _I, _V]),
@@ -206,6 +227,7 @@ SIGNATURES = {
     "m3_attention_fwd": (c_int, [_V, _I, _I, _I, _I, _I, _V, _V, _V]),
     "m3_attention_bwd_ws_elems": (c_int64, [_I, _I, _I, _I]),
     "m3_attention_bwd": (c_int, [_V, _V, _V, _V, _I, _I, _I, _I, _I, _V, _V, _V]),
+    "m3_attention_plan": (c_int, [_I, _I, _I, POINTER(AttentionPlan)]),
     "m3_cast_matrix": (c_int, [_V, _I, _I, _I, _I, _V, _I, _V]),
     "m3_cast_batch": (c_int, [_V, _I, _I, _I, _V]),
     "m3_add_f32": (c_int, [_V, _V, _L, _V]),

@@ -61,9 +61,25 @@ extern "C" int m3_attention_fwd(const void *qkv, int dtype, int B, int N, int he
   M3_REQUIRE(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)o % 16) == 0, "m3_attention_fwd: alignment");
   const float scale = 1.0f / sqrtf((float)dh);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == M3_F32) return launch_attention_fwd_f32(qkv, B, N, heads, dh, o, lse, scale, s);
-  if (N <= ATTN_KEYS) return launch_attention_fwd_res(dtype, qkv, B, N, heads, dh, o, lse, scale, s);
-  return launch_attention_fwd_stream(dtype, qkv, B, N, heads, dh, o, lse, scale, s);
+  switch (attn_family(dtype, N)) {
+    case ATTN_F32: return launch_attention_fwd_f32(qkv, B, N, heads, dh, o, lse, scale, s);
+    case ATTN_RES: return launch_attention_fwd_res(dtype, qkv, B, N, heads, dh, o, lse, scale, s);
+    default: return launch_attention_fwd_stream(dtype, qkv, B, N, heads, dh, o, lse, scale, s);
+  }
+}
+
+extern "C" int m3_attention_plan(int dtype, int N, int dh, m3_attention_plan_out *p) {
+  M3_REQUIRE(p, "m3_attention_plan: null output");
+  M3_REQUIRE(dtype_ok(dtype), "m3_attention_plan: bad dtype");
+  M3_REQUIRE(dh == 32 || dh == 64, "m3_attention_plan: head dim %d not in {32, 64}", dh);
+  M3_REQUIRE(N > 0, "m3_attention_plan: bad N");
+  const AttnFamily f = attn_family(dtype, N);
+  *p = m3_attention_plan_out{};
+  p->fwd_family = p->bwd_family = f == ATTN_F32 ? M3_ATTN_F32 : f == ATTN_RES ? M3_ATTN_RESIDENT : M3_ATTN_STREAMED;
+  p->fwd_key_tiles = f == ATTN_RES ? attn_res_fwd_nkt(N) : 0;
+  p->bwd_tiles_per_wave = f == ATTN_RES ? attn_res_bwd_kte(N, dh) : 0;
+  p->bwd_key_blocks = attn_key_blocks(N);
+  return M3_OK;
 }
 
 extern "C" int64_t m3_attention_bwd_ws_elems(int B, int N, int heads, int dh) {
@@ -80,9 +96,9 @@ extern "C" int m3_attention_bwd(const void *qkv, const void *o, const void *d_o,
   if (N <= ATTN_KEYS) dq_ws = nullptr;
   const float scale = 1.0f / sqrtf((float)dh);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype != M3_F32 && N <= ATTN_KEYS)
-    return launch_attention_bwd_res(dtype, qkv, o, d_o, lse, B, N, heads, dh, dqkv, scale, s);
-  const int rc = dtype == M3_F32 ? launch_attention_bwd_f32(qkv, o, d_o, lse, B, N, heads, dh, dqkv, dq_ws, scale, s)
+  const AttnFamily f = attn_family(dtype, N);
+  if (f == ATTN_RES) return launch_attention_bwd_res(dtype, qkv, o, d_o, lse, B, N, heads, dh, dqkv, scale, s);
+  const int rc = f == ATTN_F32 ? launch_attention_bwd_f32(qkv, o, d_o, lse, B, N, heads, dh, dqkv, dq_ws, scale, s)
                                  : launch_attention_bwd_stream(dtype, qkv, o, d_o, lse, B, N, heads, dh, dqkv, dq_ws, scale, s);
   if (rc || N <= ATTN_KEYS) return rc;
   return launch_dq_reduce(dtype, dq_ws, B, N, heads, dh, dqkv, s);

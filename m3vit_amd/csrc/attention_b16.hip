@@ -793,10 +793,8 @@ static int launch_attention_bwd_stream_t(const void *qkv, const void *o, const v
   return check_launch("m3_attention_bwd");
 }
 
-static inline int attn_res_fwd_nkt(int N) { return ((N + 15) / 16 + 3) / 4 * 4; }      // key tiles rounded up to 4, 8, 12, 16
 static size_t attn_res_fwd_lds(int N, int dh) { return (size_t)2 * attn_res_fwd_nkt(N) * 16 * dh * 2; }
-// tiles per wave of the LDS-resident backward for N keys: ceil(key tiles / waves); LDS of that instance
-static inline int attn_res_bwd_kte(int N, int dh) { const int nw = dh == 32 ? 4 : 8; return ((N + 15) / 16 + nw - 1) / nw; }
+// LDS of the LDS-resident backward instance for N keys (attention_dev.h: attn_res_bwd_kte)
 static size_t attn_res_bwd_lds(int N, int dh) {
   const size_t np = (N + 31) & ~31;
   const size_t nkey = (size_t)attn_res_bwd_kte(N, dh) * (dh == 32 ? 4 : 8) * 16;

@@ -19,6 +19,14 @@ static inline AttnBwdWs attn_bwd_ws(int B, int N, int heads, int dh) {
   return AttnBwdWs{slabs, slabs + (int64_t)B * N * heads};
 }
 
+// Which family of kernels takes a call (attention.hip dispatches by it, m3_attention_plan reports it), and the template
+// instance of the LDS-resident 16-bit kernels (attention_b16.hip launches by them)
+enum AttnFamily { ATTN_F32, ATTN_RES, ATTN_STREAM };
+static inline AttnFamily attn_family(int dtype, int N) { return dtype == M3_F32 ? ATTN_F32 : N <= ATTN_KEYS ? ATTN_RES : ATTN_STREAM; }
+static inline int attn_res_fwd_nkt(int N) { return ((N + 15) / 16 + 3) / 4 * 4; }      // key tiles rounded up to 4, 8, 12, 16
+// tiles per wave of the LDS-resident backward for N keys: ceil(key tiles / waves)
+static inline int attn_res_bwd_kte(int N, int dh) { const int nw = dh == 32 ? 4 : 8; return ((N + 15) / 16 + nw - 1) / nw; }
+
 // attention_f32.hip
 int launch_attention_fwd_f32(const void *qkv, int B, int N, int heads, int dh, void *o, float *lse, float scale, hipStream_t s);
 int launch_attention_bwd_f32(const void *qkv, const void *o, const void *d_o, const float *lse, int B, int N, int heads, int dh,

@@ -65,29 +65,34 @@ static GemmKernel choose_kernel(const GemmDev &d, int dtype) {
   return GEMM_STAGED;
 }
 
-extern "C" int m3_gemm_nt(const m3_gemm_args *a, void *stream) {
-  M3_REQUIRE(a && a->A && a->B && a->C, "m3_gemm_nt: null operand");
-  M3_REQUIRE(dtype_ok(a->dtype), "m3_gemm_nt: bad dtype %d", a->dtype);
+// What m3_gemm_nt does with a call, short of launching it: the checks, the kernels' argument block (pointers are copied,
+// never read), the kernel, the epilogue kind it is launched with and the tile order.  m3_gemm_nt launches from it,
+// m3_gemm_plan reports it
+struct GemmLaunch { GemmDev d; GemmKernel kernel; int epi, tile_m, tile_n; bool empty; };
+static int gemm_prepare(const m3_gemm_args *a, const char *who, GemmLaunch &L) {
+  M3_REQUIRE(a && a->A && a->B && a->C, "%s: null operand", who);
+  M3_REQUIRE(dtype_ok(a->dtype), "%s: bad dtype %d", who, a->dtype);
   const int es = dtype_size(a->dtype);
-  M3_REQUIRE(a->M >= 0 && a->N > 0 && a->K > 0, "m3_gemm_nt: bad shape M=%lld N=%d K=%d", (long long)a->M, a->N, a->K);
-  M3_REQUIRE((a->K * es) % 16 == 0, "m3_gemm_nt: K*elem (%d) must be a multiple of 16 bytes", a->K * es);
-  M3_REQUIRE((a->lda * es) % 16 == 0 && (a->ldb * es) % 16 == 0, "m3_gemm_nt: lda/ldb rows must be 16-byte aligned");
+  M3_REQUIRE(a->M >= 0 && a->N > 0 && a->K > 0, "%s: bad shape M=%lld N=%d K=%d", who, (long long)a->M, a->N, a->K);
+  M3_REQUIRE((a->K * es) % 16 == 0, "%s: K*elem (%d) must be a multiple of 16 bytes", who, a->K * es);
+  M3_REQUIRE((a->lda * es) % 16 == 0 && (a->ldb * es) % 16 == 0, "%s: lda/ldb rows must be 16-byte aligned", who);
   M3_REQUIRE(((uintptr_t)a->A % 16) == 0 && ((uintptr_t)a->B % 16) == 0 && ((uintptr_t)a->C % 16) == 0,
-             "m3_gemm_nt: operands must be 16-byte aligned");
-  M3_REQUIRE(a->N % 4 == 0 && a->ldc % 4 == 0, "m3_gemm_nt: N and ldc must be multiples of 4");
-  M3_REQUIRE(a->lda >= a->K && a->ldb >= a->K && a->ldc >= a->N, "m3_gemm_nt: leading dimension too small");
-  M3_REQUIRE(a->c_dtype == M3_F32 || a->c_dtype == a->dtype, "m3_gemm_nt: c_dtype must be f32 or the operand dtype");
-  M3_REQUIRE(a->G >= 1, "m3_gemm_nt: G must be >= 1");
-  M3_REQUIRE((a->group_offsets == nullptr) == (a->tile_starts == nullptr), "m3_gemm_nt: group_offsets/tile_starts go together");
-  M3_REQUIRE(a->G == 1 || a->group_offsets, "m3_gemm_nt: grouped call needs group_offsets");
-  M3_REQUIRE(!a->a_row_idx || a->a_row_div >= 1, "m3_gemm_nt: a_row_div must be >= 1");
-  M3_REQUIRE(!a->pre_out || a->ld_pre % 4 == 0, "m3_gemm_nt: ld_pre % 4");
-  M3_REQUIRE(!a->gelu_grad_pre || a->ld_gpre % 4 == 0, "m3_gemm_nt: ld_gpre % 4");
-  M3_REQUIRE(!a->residual || a->ld_res % 4 == 0, "m3_gemm_nt: ld_res % 4");
-  M3_REQUIRE(!a->row_scale || a->row_scale_div >= 1, "m3_gemm_nt: row_scale_div must be >= 1");
-  if (a->M == 0) return M3_OK;
+             "%s: operands must be 16-byte aligned", who);
+  M3_REQUIRE(a->N % 4 == 0 && a->ldc % 4 == 0, "%s: N and ldc must be multiples of 4", who);
+  M3_REQUIRE(a->lda >= a->K && a->ldb >= a->K && a->ldc >= a->N, "%s: leading dimension too small", who);
+  M3_REQUIRE(a->c_dtype == M3_F32 || a->c_dtype == a->dtype, "%s: c_dtype must be f32 or the operand dtype", who);
+  M3_REQUIRE(a->G >= 1, "%s: G must be >= 1", who);
+  M3_REQUIRE((a->group_offsets == nullptr) == (a->tile_starts == nullptr), "%s: group_offsets/tile_starts go together", who);
+  M3_REQUIRE(a->G == 1 || a->group_offsets, "%s: grouped call needs group_offsets", who);
+  M3_REQUIRE(!a->a_row_idx || a->a_row_div >= 1, "%s: a_row_div must be >= 1", who);
+  M3_REQUIRE(!a->pre_out || a->ld_pre % 4 == 0, "%s: ld_pre %% 4", who);
+  M3_REQUIRE(!a->gelu_grad_pre || a->ld_gpre % 4 == 0, "%s: ld_gpre %% 4", who);
+  M3_REQUIRE(!a->residual || a->ld_res % 4 == 0, "%s: ld_res %% 4", who);
+  M3_REQUIRE(!a->row_scale || a->row_scale_div >= 1, "%s: row_scale_div must be >= 1", who);
+  L.empty = a->M == 0;
+  if (L.empty) return M3_OK;
 
-  GemmDev d;
+  GemmDev &d = L.d;
   d.A = (const char *)a->A; d.lda_b = a->lda * es;
   d.a_row_idx = a->a_row_idx; d.a_row_div = a->a_row_idx ? a->a_row_div : 1;
   d.a_row_sh = div_shift(d.a_row_div);
@@ -107,26 +112,47 @@ extern "C" int m3_gemm_nt(const m3_gemm_args *a, void *stream) {
             (!a->gelu_grad_pre || a->ld_gpre % 8 == 0) && (!a->residual || a->ld_res % 8 == 0)) ? 1 : 0;
   // 32-bit per-lane byte offsets: A rows (gathered source rows must be < M) and one B group must fit 4 GiB
   M3_REQUIRE((a->M + 1) * a->lda * es < ((int64_t)1 << 32) && (int64_t)a->N * a->ldb * es < ((int64_t)1 << 32),
-             "m3_gemm_nt: operand panel exceeds the 4 GiB reach of the 32-bit lane offsets");
+             "%s: operand panel exceeds the 4 GiB reach of the 32-bit lane offsets", who);
 
-  const GemmKernel kernel = choose_kernel(d, a->dtype);
+  const GemmKernel kernel = L.kernel = choose_kernel(d, a->dtype);
+  // the register-staged kernels have the run-time-flag epilogue only
+  L.epi = kernel == GEMM_BIG || kernel == GEMM_DMA ? epilogue_kind(a) : DMA_EPI_ANY;
   // tile order (gemm_dev.h: tile_of) of the kernel chosen.  128-row tiles: bands of four row tiles when a group's weight
   // does not fit an XCD's L2 beside the rows (> 2 MB: the ViT-Base N = 2304 / 3072 launches and K = 3072).  256-row tiles:
   // row-tile major always - a tile's A rows at K >= 2048 are 1 MB and more, four of them do not sit in an L2 (counters:
   // banded +13 % fetch).  A grouped call's grid is sized for the upper bound of row tiles: one partial tile per group
-  const int tile_m = kernel == GEMM_BIG ? BIG_B : kernel == GEMM_STAGED_TALL ? 160 : BM;
-  const int tile_n = kernel == GEMM_BIG ? BIG_B : BN;
+  const int tile_m = L.tile_m = kernel == GEMM_BIG ? BIG_B : kernel == GEMM_STAGED_TALL ? 160 : BM;
+  const int tile_n = L.tile_n = kernel == GEMM_BIG ? BIG_B : BN;
   const int band = gemm_env().band > 0 ? gemm_env().band : ((int64_t)a->N * a->K * es > ((int64_t)2 << 20) ? 4 : 1);
   const int64_t mt = (a->M + tile_m - 1) / tile_m + (a->group_offsets ? a->G : 0);
   d.n_tiles = (a->N + tile_n - 1) / tile_n;
   d.m_band = kernel == GEMM_BIG ? 1 : band;
-  M3_REQUIRE(mt * d.n_tiles < (int64_t)1 << 30, "m3_gemm_nt: grid too large");
+  M3_REQUIRE(mt * d.n_tiles < (int64_t)1 << 30, "%s: grid too large", who);
   d.m_tiles_max = (int)mt;
+  return M3_OK;
+}
 
+extern "C" int m3_gemm_nt(const m3_gemm_args *a, void *stream) {
+  GemmLaunch L;
+  if (int rc = gemm_prepare(a, "m3_gemm_nt", L)) return rc;
+  if (L.empty) return M3_OK;
   hipStream_t s = (hipStream_t)stream;
-  switch (kernel) {
-    case GEMM_BIG: return launch_gemm_big(d, a->dtype, epilogue_kind(a), s);
-    case GEMM_DMA: return launch_gemm_dma(d, a->dtype, epilogue_kind(a), s);
-    default: return launch_gemm_staged(d, a->dtype, kernel == GEMM_STAGED_TALL, s);
+  switch (L.kernel) {
+    case GEMM_BIG: return launch_gemm_big(L.d, a->dtype, L.epi, s);
+    case GEMM_DMA: return launch_gemm_dma(L.d, a->dtype, L.epi, s);
+    default: return launch_gemm_staged(L.d, a->dtype, L.kernel == GEMM_STAGED_TALL, s);
   }
+}
+
+extern "C" int m3_gemm_plan(const m3_gemm_args *a, m3_gemm_plan_out *p) {
+  M3_REQUIRE(p, "m3_gemm_plan: null output");
+  GemmLaunch L;
+  if (int rc = gemm_prepare(a, "m3_gemm_plan", L)) return rc;
+  *p = m3_gemm_plan_out{};
+  p->kernel = M3_GEMM_NONE;
+  if (L.empty) return M3_OK;
+  p->kernel = L.kernel == GEMM_BIG ? M3_GEMM_BIG : L.kernel == GEMM_DMA ? M3_GEMM_DMA : L.kernel == GEMM_STAGED_TALL ? M3_GEMM_STAGED_TALL : M3_GEMM_STAGED;
+  p->epilogue = L.epi; p->tile_m = L.tile_m; p->tile_n = L.tile_n; p->m_band = L.d.m_band; p->vec8 = L.d.vec8;
+  p->n_tiles = L.d.n_tiles; p->m_tiles_max = L.d.m_tiles_max;
+  return M3_OK;
 }

@@ -436,24 +436,26 @@ static WgradKernel wgrad_demote(WgradKernel kern, const m3_wgrad_args *a, const 
   return kern;
 }
 
-extern "C" int m3_wgrad_tn(const m3_wgrad_args *a, void *stream) {
-  M3_REQUIRE(a && a->dC && a->A && (a->ws || a->direct_dW), "m3_wgrad_tn: null operand");
-  M3_REQUIRE(dtype_ok(a->dtype), "m3_wgrad_tn: bad dtype");
+// What m3_wgrad_tn does with a call before it launches anything: the checks of the call itself, the kernels' argument block
+// (pointers are copied, never read) and the kernel after wgrad_demote.  m3_wgrad_tn launches from it, m3_wgrad_kernel reports it.
+// (The descriptors behind a->prev do not enter the choice: the launch checks them, wgrad_take_prev.)
+static int wgrad_prepare(const m3_wgrad_args *a, const char *who, WgradDev &d, WgradKernel &kern) {
+  M3_REQUIRE(a && a->dC && a->A && (a->ws || a->direct_dW), "%s: null operand", who);
+  M3_REQUIRE(dtype_ok(a->dtype), "%s: bad dtype", who);
   const int es = dtype_size(a->dtype);
-  M3_REQUIRE(a->N > 0 && a->K > 0 && a->M >= 0 && a->G >= 1 && a->splits >= 1, "m3_wgrad_tn: bad shape");
-  M3_REQUIRE(a->M < ((int64_t)1 << 31), "m3_wgrad_tn: M exceeds the 32-bit row indices");
-  M3_REQUIRE((a->N * es) % 16 == 0 && (a->K * es) % 16 == 0, "m3_wgrad_tn: N*elem and K*elem must be multiples of 16 bytes");
-  M3_REQUIRE((a->lddc * es) % 16 == 0 && (a->lda * es) % 16 == 0, "m3_wgrad_tn: rows must be 16-byte aligned");
-  M3_REQUIRE(((uintptr_t)a->dC % 16) == 0 && ((uintptr_t)a->A % 16) == 0 && ((uintptr_t)a->ws % 16) == 0, "m3_wgrad_tn: alignment");
+  M3_REQUIRE(a->N > 0 && a->K > 0 && a->M >= 0 && a->G >= 1 && a->splits >= 1, "%s: bad shape", who);
+  M3_REQUIRE(a->M < ((int64_t)1 << 31), "%s: M exceeds the 32-bit row indices", who);
+  M3_REQUIRE((a->N * es) % 16 == 0 && (a->K * es) % 16 == 0, "%s: N*elem and K*elem must be multiples of 16 bytes", who);
+  M3_REQUIRE((a->lddc * es) % 16 == 0 && (a->lda * es) % 16 == 0, "%s: rows must be 16-byte aligned", who);
+  M3_REQUIRE(((uintptr_t)a->dC % 16) == 0 && ((uintptr_t)a->A % 16) == 0 && ((uintptr_t)a->ws % 16) == 0, "%s: alignment", who);
   M3_REQUIRE(!a->direct_dW || (a->splits == 1 && a->chunk_rows == 0 && ((uintptr_t)a->direct_dW % 16) == 0 && !a->bias_ws),
-             "m3_wgrad_tn: direct mode needs splits == 1, no balanced units, a 16-byte aligned dW and no bias slabs");
-  M3_REQUIRE(!a->direct_db || a->direct_dW, "m3_wgrad_tn: direct_db goes with direct_dW");
-  M3_REQUIRE(a->G == 1 || a->group_offsets, "m3_wgrad_tn: grouped call needs group_offsets");
-  M3_REQUIRE(!a->a_row_idx || a->a_row_div >= 1, "m3_wgrad_tn: a_row_div");
-  WgradDev d;
+             "%s: direct mode needs splits == 1, no balanced units, a 16-byte aligned dW and no bias slabs", who);
+  M3_REQUIRE(!a->direct_db || a->direct_dW, "%s: direct_db goes with direct_dW", who);
+  M3_REQUIRE(a->G == 1 || a->group_offsets, "%s: grouped call needs group_offsets", who);
+  M3_REQUIRE(!a->a_row_idx || a->a_row_div >= 1, "%s: a_row_div", who);
   d.dC = (const char *)a->dC; d.lddc_b = a->lddc * es; d.c_row_idx = a->c_row_idx;
-  M3_REQUIRE(a->c_row_idx || (!a->c_row_scale && a->c_row_div <= 1), "m3_wgrad_tn: c_row_div / c_row_scale need c_row_idx");
-  M3_REQUIRE(a->c_row_div >= 0, "m3_wgrad_tn: c_row_div");
+  M3_REQUIRE(a->c_row_idx || (!a->c_row_scale && a->c_row_div <= 1), "%s: c_row_div / c_row_scale need c_row_idx", who);
+  M3_REQUIRE(a->c_row_div >= 0, "%s: c_row_div", who);
   d.c_row_div = (a->c_row_idx && a->c_row_div >= 1) ? a->c_row_div : 1;
   d.c_row_scale = a->c_row_scale;
   d.c_row_sh = div_shift(d.c_row_div);
@@ -464,11 +466,32 @@ extern "C" int m3_wgrad_tn(const m3_wgrad_args *a, void *stream) {
   d.direct_dW = a->direct_dW; d.direct_db = a->direct_dW ? a->direct_db : nullptr;
   d.direct_beta = a->direct_beta; d.direct_beta_db = a->direct_beta_db;
   M3_REQUIRE(a->chunk_rows >= 0 && (a->chunk_rows == 0 || (a->group_offsets && a->chunk_rows % WG_ROWS == 0 && a->units >= 1 && a->G <= 64)),
-             "m3_wgrad_tn: balanced mode needs group_offsets, G <= 64, chunk_rows a multiple of %d and units >= 1", WG_ROWS);
+             "%s: balanced mode needs group_offsets, G <= 64, chunk_rows a multiple of %d and units >= 1", who, WG_ROWS);
   d.chunk_rows = a->chunk_rows;
+  kern = wgrad_demote(wgrad_kernel_of_shape(a->N, a->K, a->G, a->dtype), a, d);
+  return M3_OK;
+}
+
+extern "C" int m3_wgrad_kernel(const m3_wgrad_args *a, m3_wgrad_kernel_out *out) {
+  M3_REQUIRE(out, "m3_wgrad_kernel: null output");
+  WgradDev d;
+  WgradKernel kern;
+  if (int rc = wgrad_prepare(a, "m3_wgrad_kernel", d, kern)) return rc;
+  *out = m3_wgrad_kernel_out{};
+  out->kernel = kern == WGRAD_BIG ? M3_WGRAD_KERNEL_BIG : kern == WGRAD_SKINNY ? M3_WGRAD_KERNEL_SKINNY : kern == WGRAD_DMA ? M3_WGRAD_KERNEL_DMA : M3_WGRAD_KERNEL_STAGED;
+  out->gather_c = a->c_row_idx != nullptr; out->gather_a = a->a_row_idx != nullptr; out->scale_c = a->c_row_scale != nullptr;
+  out->tile_n = kern == WGRAD_BIG ? BG_T : WG_T;
+  out->tile_k = kern == WGRAD_BIG ? BG_T : kern == WGRAD_SKINNY ? a->K : WG_T;
+  return M3_OK;
+}
+
+extern "C" int m3_wgrad_tn(const m3_wgrad_args *a, void *stream) {
+  WgradDev d;
+  WgradKernel kern;
+  if (int rc = wgrad_prepare(a, "m3_wgrad_tn", d, kern)) return rc;
+  const int es = dtype_size(a->dtype);
   hipStream_t s = (hipStream_t)stream;
   const bool gc = a->c_row_idx != nullptr, ga = a->a_row_idx != nullptr, sc = a->c_row_scale != nullptr;
-  const WgradKernel kern = wgrad_demote(wgrad_kernel_of_shape(a->N, a->K, a->G, a->dtype), a, d);
   const bool big = kern == WGRAD_BIG;
   // the previous call's slab reduction (a->prev): in front of this launch (128-wide kernels), or as its own launch.  In direct
   // mode this launch read-add-writes dW while those blocks run: they must not write the same tensor

@@ -390,6 +390,15 @@ def gemm_nt(A, B, C, *, M=None, bias=None, act=M3_ACT_NONE, pre_out=None, gelu_g
     return C
 
 
+def gemm_plan(a: GemmArgs) -> _lib.GemmPlan:
+    """What m3_gemm_nt would do with the argument struct `a` (m3_gemm_plan in include/m3vit_hip.h): .kernel / .epilogue
+    (names: _lib.GEMM_KERNELS / _lib.GEMM_EPILOGUES), the tile and the tile order.  Host code: launches nothing, reads no
+    operand."""
+    p = _lib.GemmPlan()
+    check(lib().m3_gemm_plan(byref(a), byref(p)), "m3_gemm_plan")
+    return p
+
+
 def gemm_set_big(mode: int):
     """which gemm_nt calls take the 256 x 256-tile kernel for long contractions (include/m3vit_hip.h: m3_gemm_set_big):
     0 never, 1 every call it can run, 2 (default) those with enough tiles to fill the chip, -1 re-read M3_GEMM_BIG"""
@@ -649,6 +658,14 @@ def wgrad_skinny(N, K, G=1) -> bool:
     return bool(lib().m3_wgrad_skinny(int(N), int(K), int(G)))
 
 
+def wgrad_kernel(a: WgradArgs) -> _lib.WgradKernelOut:
+    """The kernel m3_wgrad_tn would launch for the argument struct `a`, after its step-downs, and the instance flags
+    (m3_wgrad_kernel in include/m3vit_hip.h; names: _lib.WGRAD_KERNELS).  Host code: launches nothing, reads no operand."""
+    out = _lib.WgradKernelOut()
+    check(lib().m3_wgrad_kernel(byref(a), byref(out)), "m3_wgrad_kernel")
+    return out
+
+
 def colsum(dC, db, *, M=None, beta=0, c_row_idx=None, group_offsets=None, ws=None):
     _req(dC, name="dC"); _req(db, torch.float32, "db")
     G = 1 if db.dim() == 1 else db.shape[0]
@@ -804,6 +821,14 @@ def layernorm_bwd_reduce(ws, nblk, D, table: LnGradTable, first, count, beta=1):
 
 
 # ------------------------------------------------------------------------ attention
+def attention_plan(dtype, N, dh) -> _lib.AttentionPlan:
+    """kernel family and instance of attention_fwd / attention_bwd for (dtype, N, dh) (m3_attention_plan in
+    include/m3vit_hip.h; names: _lib.ATTN_FAMILIES).  Host code."""
+    p = _lib.AttentionPlan()
+    check(lib().m3_attention_plan(dt_code(dtype), int(N), int(dh), byref(p)), "m3_attention_plan")
+    return p
+
+
 def attention_fwd(qkv, B, N, heads, dh, o, lse):
     _act(qkv, "qkv", B * N * 3 * heads * dh); _req(o, qkv.dtype, "o", B * N * heads * dh)
     _req(lse, torch.float32, "lse", B * heads * N)

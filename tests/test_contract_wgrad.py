@@ -4,13 +4,20 @@ expert, direct mode, a WgradQueue ride-along, G > 64; beta = 1 onto a non-zero p
 with m3_wgrad_reduce, m3_wgrad_reduce_grouped and m3_wgrad_bias_reduce called directly; m3_colsum.  Every workspace is
 exactly the size the library reports and sentinel-NaN-filled (a read of a slab slot nobody wrote shows as NaN), every output
 is guarded, inputs keep their bits, and a second call under a different workspace fill must give the same bits (the slab
-sums run in a fixed order)."""
+sums run in a fixed order).
+
+Every run() call states the kernel it is meant to land on AFTER the library's step-downs (wgrad.hip: wgrad_demote) and
+asserts it, with the instance flags (gathered dC rows, gathered A rows, per-row factor), through m3_wgrad_kernel on the
+argument struct ops.wgrad_tn fills and launches.  plan_args() builds the same struct from dummy addresses (no GPU):
+tests/test_launch_paths_cpu.py pins the cases with it, tests/test_engine_launch_census_gpu.py compares the engine's
+launches with them (cases())."""
 from ctypes import byref
 
 import pytest
 import torch
 
 import kernel_contract as kc
+import launch_signature as ls
 
 pytestmark = pytest.mark.gpu
 F32, F16, BF16 = torch.float32, torch.float16, torch.bfloat16
@@ -65,10 +72,34 @@ def reference(dC, A, N, K, G, grp, Mv, splits, dtype, c_idx=None, c_div=1, c_sca
     return W, db, bW, bdb
 
 
-def run(ops, dtype, M, N, K, *, G=1, counts=None, splits=None, beta=0, want_db=True, c_idx=None, c_div=1, c_scale=None,
+def plan_args(ops, dtype, M, N, K, *, G=1, grouped=False, splits=None, want_db=True, gc=False, c_div=1, sc=False, ga=False,
+              a_div=1):
+    """the argument struct ops.wgrad_tn fills for a run() call, with dummy addresses in place of the operands: the same
+    m3_wgrad_plan request, the same mode fields.  Host only"""
+    p = ops.wgrad_launch_plan(M, N, K, G, dtype, grouped=grouped, bias=want_db, splits=splits or 0, direct_ok=ops._WGRAD_DIRECT)
+    on = lambda cond: ls.DUMMY if cond else None                                  # noqa: E731
+    a = ops.WgradArgs()
+    a.dC, a.lddc, a.c_row_idx, a.c_row_div, a.c_row_scale = ls.DUMMY, N, on(gc), c_div, on(sc)
+    a.A, a.lda, a.a_row_idx, a.a_row_div = ls.DUMMY, K, on(ga), a_div
+    a.M, a.N, a.K, a.G = M, N, K, G
+    a.group_offsets = on(grouped)
+    a.splits, a.chunk_rows, a.units = p.splits, p.chunk_rows, p.units
+    a.ws, a.dtype = ls.DUMMY, ops.dt_code(dtype)
+    a.direct_dW, a.direct_db = on(p.direct), on(p.direct and want_db)
+    a.bias_ws = on(want_db and not p.direct)
+    return a
+
+
+def run(ops, dtype, M, N, K, *, kernel, G=1, counts=None, splits=None, beta=0, want_db=True, c_idx=None, c_div=1, c_scale=None,
         a_idx=None, a_div=1, dC=None, A=None, tag=""):
     """one ops.wgrad_tn call with guarded dW / db and an exactly sized, sentinel-filled workspace; checks values, guards,
-    inputs and bitwise repeatability under a different workspace fill.  Returns the worst err / bound ratio."""
+    inputs and bitwise repeatability under a different workspace fill.  kernel: the one the call is meant to land on after
+    the library's step-downs - asserted, with the instance flags, on the struct that is launched.  Returns the worst
+    err / bound ratio."""
+    flags = dict(gc=c_idx is not None, ga=a_idx is not None, sc=c_scale is not None)
+    want = ls.wgrad_signature(ops, plan_args(ops, dtype, M, N, K, G=G, grouped=counts is not None, splits=splits, want_db=want_db,
+                                             c_div=c_div, a_div=a_div, **flags))
+    assert (want.get("kernel"), want.get("gc"), want.get("ga"), want.get("sc")) == (kernel, *map(int, flags.values())), f"{want} is not {kernel} {flags}"
     if counts is not None:
         off, grp, Mv = routing(G, counts)
     else:
@@ -96,7 +127,11 @@ def run(ops, dtype, M, N, K, *, G=1, counts=None, splits=None, beta=0, want_db=T
     shape = (G, N, K) if G > 1 else (N, K)
     kw = dict(M=M, beta=beta, splits=sp, ws=ws, c_row_idx=c_idx, c_row_div=c_div, c_row_scale=c_scale, a_row_idx=a_idx,
               a_row_div=a_div, group_offsets=off)
-    ops.wgrad_tn(dC, A, dW.view(shape), db=db.view(G, N) if want_db and G > 1 else (db.view(N) if want_db else None), **kw)
+    with ls.Recorder(ops) as rec:
+        ops.wgrad_tn(dC, A, dW.view(shape), db=db.view(G, N) if want_db and G > 1 else (db.view(N) if want_db else None), **kw)
+    ((_, launched, _),) = rec.calls
+    got = ls.wgrad_signature(ops, launched)
+    assert got == want, f"the call ran\n  {got}\nand states\n  {want}"
     torch.cuda.synchronize()
     kc.unchanged(snap); wcheck(); dWcheck()
     if want_db:
@@ -144,72 +179,226 @@ class knobs:
             self.ops.wgrad_set_big(-1)
 
 
-# kernel id: dtype, N, K, wgrad_set_dma, wgrad_set_big, bias column sums
+# kernel id: dtype, N, K, wgrad_set_dma, wgrad_set_big, bias column sums, the kernel a plain call is meant to run
 KERNELS = {
-    "staged_f16": (F16, 384, 192, 0, 0, True),
-    "staged_bf16": (BF16, 132 + 4, 200, 0, 0, True),
-    "staged_f32": (F32, 132, 68, 0, 0, True),
-    "dma_f16": (F16, 384, 192, 2, 0, True),
-    "dma_bf16": (BF16, 136, 200, 2, 0, True),
-    "dma_f32": (F32, 132, 68, 2, 0, True),
-    "big_f16": (F16, 256, 512, None, 1, True),
-    "big_bf16": (BF16, 512, 256, None, 1, True),
-    "skinny16_f16": (F16, 384, 16, None, None, False),
-    "skinny32_bf16": (BF16, 384, 32, None, None, False),
+    "staged_f16": (F16, 384, 192, 0, 0, True, "staged"),
+    "staged_bf16": (BF16, 132 + 4, 200, 0, 0, True, "staged"),
+    "staged_f32": (F32, 132, 68, 0, 0, True, "staged"),
+    "dma_f16": (F16, 384, 192, 2, 0, True, "dma"),
+    "dma_bf16": (BF16, 136, 200, 2, 0, True, "dma"),
+    "dma_f32": (F32, 132, 68, 2, 0, True, "dma"),
+    "big_f16": (F16, 256, 512, None, 1, True, "big"),
+    "big_bf16": (BF16, 512, 256, None, 1, True, "big"),
+    "skinny16_f16": (F16, 384, 16, None, None, False, "skinny"),
+    "skinny32_bf16": (BF16, 384, 32, None, None, False, "skinny"),
+    "skinny32_f16": (F16, 384, 32, None, None, False, "skinny"),
+    "skinny16_bf16": (BF16, 384, 16, None, None, False, "skinny"),
+    "skinny16_f32": (F32, 384, 16, None, None, False, "skinny"),          # the engine's fp32 router weight (E = 16)
+    "skinny32_f32": (F32, 384, 32, None, None, False, "skinny"),
 }
+SPLITS = [1, 2, 3, 5, 7]
+GROUPED_KERNELS = ["staged_f16", "dma_f16", "dma_f32", "big_f16", "dma_bf16", "big_bf16"]
+GROUPED_SPLITS = [None, 1, 4]
+GROUPED_COUNTS = [0, 700, 0, 45, 129, 0]
 
 
-@pytest.mark.parametrize("splits", [1, 2, 3, 5, 7])
+def plain_kernel(kern, splits):
+    """the kernel of a plain call of KERNELS[kern] cut into `splits` parts.  The streaming kernel writes slabs only: with one
+    part ops.wgrad_tn takes direct mode, and the call steps down to the 128 x 128 kernel of the default m3_wgrad_set_dma
+    rule - LDS-DMA for fp32, register-staged for these small 16-bit weights"""
+    dtype, stated = KERNELS[kern][0], KERNELS[kern][6]
+    if stated == "skinny" and splits == 1:
+        return "dma" if dtype == F32 else "staged"
+    return stated
+
+
+def scaled_kernel(kern):
+    """the kernel of the grouped call with a per-row factor (gathered dC rows scaled by the gate score): the 256 x 256
+    kernel has the factor for fp16 only, the 128-wide LDS-DMA kernel for fp16 and fp32 - a bf16 call steps down to the
+    register-staged kernel from either"""
+    dtype, stated = KERNELS[kern][0], KERNELS[kern][6]
+    return "staged" if dtype == BF16 else stated
+
+
+@pytest.mark.parametrize("splits", SPLITS)
 @pytest.mark.parametrize("kern", list(KERNELS))
 def test_wgrad_kernels_and_slab_splits(ops, kern, splits):
     """splits = 1 is direct mode for the 128 / 256 tiles (the kernel adds into dW itself, no slabs); 2..7 slab mode"""
-    dtype, N, K, dma, big, want_db = KERNELS[kern]
+    dtype, N, K, dma, big, want_db, kernel = KERNELS[kern]
     M = 333
     with knobs(ops, dma, big):
         if kern.startswith("skinny"):
             assert ops.wgrad_skinny(N, K)
         if kern.startswith("big"):
             assert ops.wgrad_tile(N, K, dtype) == (256, 256)
-        w = run(ops, dtype, M, N, K, splits=splits, want_db=want_db, tag=f"{kern}/{splits}")
-        w = max(w, run(ops, dtype, M, N, K, splits=splits, want_db=want_db, beta=1, tag=f"{kern}/{splits}/beta1"))
+        kernel = plain_kernel(kern, splits)
+        w = run(ops, dtype, M, N, K, kernel=kernel, splits=splits, want_db=want_db, tag=f"{kern}/{splits}")
+        w = max(w, run(ops, dtype, M, N, K, kernel=kernel, splits=splits, want_db=want_db, beta=1, tag=f"{kern}/{splits}/beta1"))
     assert w < 1
 
 
-@pytest.mark.parametrize("splits", [None, 1, 4])
-@pytest.mark.parametrize("kern", ["staged_f16", "dma_f16", "dma_f32", "big_f16", "dma_bf16", "big_bf16"])
+@pytest.mark.parametrize("splits", GROUPED_SPLITS)
+@pytest.mark.parametrize("kern", GROUPED_KERNELS)
 def test_wgrad_grouped_balanced_and_direct(ops, kern, splits):
     """grouped: an empty first / middle / last expert and one hot one (balanced units give it more workgroups), slack rows
     past group_offsets[G]; rows gathered (a_row_idx / 2) and dC read through the combine's slot map (c_row_idx / k = 2) scaled
     by the gate score.  bf16 rows with a per-row factor are the one call both LDS-DMA kernels must refuse (the 256 x 256
-    kernel has the factor for fp16 only, the 128-wide one for fp16 and fp32): it has to land on the register-staged kernel"""
-    dtype, N, K, dma, big, _ = KERNELS[kern]
-    counts = [0, 700, 0, 45, 129, 0]
+    kernel has the factor for fp16 only, the 128-wide one for fp16 and fp32): it has to land on the register-staged kernel,
+    and run() asserts that it does; the fp16 and fp32 calls with a factor stay on the LDS-DMA kernel they name"""
+    dtype, N, K, dma, big, _, kernel = KERNELS[kern]
+    counts = GROUPED_COUNTS
     G, M = len(counts), sum(counts) + 19
     g = torch.Generator().manual_seed(5)
     c_idx = torch.randperm(2 * M, generator=g)[:M].to(torch.int32).cuda()
     c_scale = (torch.rand(2 * M, generator=g) + 0.5).cuda()
     a_idx = torch.randint(0, 2 * M, (M,), generator=g, dtype=torch.int32).cuda()
     with knobs(ops, dma, big):
-        w = run(ops, dtype, M, N, K, G=G, counts=counts, splits=splits, c_idx=c_idx, c_div=2, c_scale=c_scale, a_idx=a_idx,
-                a_div=2, tag=f"grouped/{kern}/{splits}")
-        w = max(w, run(ops, dtype, M, N, K, G=G, counts=counts, splits=splits, beta=1, a_idx=a_idx, a_div=2,
+        w = run(ops, dtype, M, N, K, kernel=scaled_kernel(kern), G=G, counts=counts, splits=splits, c_idx=c_idx, c_div=2,
+                c_scale=c_scale, a_idx=a_idx, a_div=2, tag=f"grouped/{kern}/{splits}")
+        w = max(w, run(ops, dtype, M, N, K, kernel=kernel, G=G, counts=counts, splits=splits, beta=1, a_idx=a_idx, a_div=2,
                        tag=f"grouped/{kern}/{splits}/beta1"))
     assert w < 1
+
+
+def many_groups_counts(G):
+    g = torch.Generator().manual_seed(G)
+    counts = torch.randint(0, 50, (G,), generator=g).tolist()
+    counts[0] = counts[G // 2] = counts[-1] = 0
+    counts[3] = 200
+    return counts, sum(counts) + 7
 
 
 @pytest.mark.parametrize("G", [65, 96])
 def test_wgrad_more_than_64_groups(ops, G):
     """G > 64: no balanced units (every group in `splits` parts) and the scalar group walk of the kernels"""
-    g = torch.Generator().manual_seed(G)
-    counts = torch.randint(0, 50, (G,), generator=g).tolist()
-    counts[0] = counts[G // 2] = counts[-1] = 0
-    counts[3] = 200
-    M = sum(counts) + 7
+    counts, M = many_groups_counts(G)
     for kern in ("staged_f16", "dma_f16"):
-        dtype, N, K, dma, big, _ = KERNELS[kern]
+        dtype, N, K, dma, big, _, kernel = KERNELS[kern]
         with knobs(ops, dma, big):
             for sp in (1, 2):
-                assert run(ops, dtype, M, 128, 64, G=G, counts=counts, splits=sp, tag=f"G{G}/{kern}/{sp}") < 1
+                assert run(ops, dtype, M, 128, 64, kernel=kernel, G=G, counts=counts, splits=sp, tag=f"G{G}/{kern}/{sp}") < 1
+
+
+# Every template instance of the three tile families (wgrad_staged.hip: WgStaged, wgrad_dma.hip: WgDma, WgBig): gathered dC rows
+# (gc), gathered A rows (ga), per-row factor on gathered dC rows (sc) by dtype, on a grouped call with balanced units
+FAMILIES = {"staged": ("staged_f16", "staged_bf16", "staged_f32"), "dma": ("dma_f16", "dma_bf16", "dma_f32"), "big": ("big_f16", "big_bf16")}
+
+
+def has_instance(kernel, dtype, gc, ga, sc):
+    """the instances the families state (the `instance()` members of the three structs)"""
+    if not sc:
+        return kernel != "big" or dtype != F32
+    if not gc:
+        return False
+    return {"staged": True, "dma": dtype != BF16, "big": dtype == F16}[kernel]
+
+
+INSTANCES = [(kernel, kern, gc, ga, sc) for kernel, kerns in FAMILIES.items() for kern in kerns
+             for gc in (0, 1) for ga in (0, 1) for sc in (0, 1) if has_instance(kernel, KERNELS[kern][0], gc, ga, sc)]
+
+
+def instance_case(kern, gc, ga, sc):
+    dtype, N, K, dma, big = KERNELS[kern][:5]
+    M = sum(GROUPED_COUNTS) + 19
+    return (dtype, M, N, K), dict(G=len(GROUPED_COUNTS), grouped=True, splits=4, gc=bool(gc), c_div=2 if gc else 1, sc=bool(sc),
+                                  ga=bool(ga), a_div=2 if ga else 1)
+
+
+def _gathers(M, gc, ga, sc, c_div, a_div, seed=5):
+    g = torch.Generator().manual_seed(seed)
+    c_idx = torch.randperm(c_div * M, generator=g)[:M].to(torch.int32).cuda() if gc else None
+    c_scale = (torch.rand(c_div * M, generator=g) + 0.5).cuda() if sc else None
+    a_idx = torch.randint(0, a_div * M, (M,), generator=g, dtype=torch.int32).cuda() if ga else None
+    return c_idx, c_scale, a_idx
+
+
+@pytest.mark.parametrize("kernel,kern,gc,ga,sc", INSTANCES)
+def test_wgrad_every_instance(ops, kernel, kern, gc, ga, sc):
+    dtype, N, K, dma, big = KERNELS[kern][:5]
+    (_, M, _, _), kw = instance_case(kern, gc, ga, sc)
+    c_idx, c_scale, a_idx = _gathers(M, gc, ga, sc, kw["c_div"], kw["a_div"])
+    with knobs(ops, dma, big):
+        assert run(ops, dtype, M, N, K, kernel=kernel, G=kw["G"], counts=GROUPED_COUNTS, splits=4, c_idx=c_idx, c_div=kw["c_div"],
+                   c_scale=c_scale, a_idx=a_idx, a_div=kw["a_div"], tag=f"instance/{kern}/{gc}{ga}{sc}") < 1
+
+
+# The weight gradients as the engine launches them (tests/test_engine_launch_census_gpu.py), under the library's default
+# m3_wgrad_set_dma / m3_wgrad_set_big rules: N and K whole tiles; the expert FC2 reads d y through the slot map with divisor
+# k = 4, scaled by the gate score, and plain A rows; the expert FC1 gathers its A rows with divisor 4; the dense weights
+# are plain with the bias column sums; the router's weight at E = 64 is a K tail without a bias.  splits 1 is direct mode,
+# 4 balanced units (grouped) or slabs (dense).  A bf16 expert FC2 on a 256 x 256 shape steps down to the register-staged kernel
+ENGINE_SHAPES = {"f32": (F32, 256, 128, "dma"), "f16": (F16, 256, 128, "staged"), "bf16": (BF16, 256, 128, "staged"),
+                 "f16_big": (F16, 256, 512, "big"), "bf16_big": (BF16, 256, 512, "big")}
+ENGINE_FORMS = {
+    "fc2": dict(grouped=True, gc=True, c_div=4, sc=True),
+    "fc1": dict(grouped=True, ga=True, a_div=4),
+    "dense": dict(),
+    "gate64": dict(want_db=False, K=64),
+}
+ENGINE = [(sh, form, sp) for sh in ENGINE_SHAPES for form in ENGINE_FORMS for sp in (1, 4) if not (sh.endswith("big") and form == "gate64")]
+
+
+def engine_case(sh, form, sp):
+    """(stated kernel, plan_args positional, keyword) of an ENGINE entry"""
+    dtype, N, K, kernel = ENGINE_SHAPES[sh]
+    kw = dict(ENGINE_FORMS[form])
+    K = kw.pop("K", K)
+    if kernel == "big" and kw.get("sc") and dtype == BF16:
+        kernel = "staged"
+    grouped = kw.get("grouped", False)
+    M = sum(GROUPED_COUNTS) + 19 if grouped else 333
+    return kernel, (dtype, M, N, K), dict(G=len(GROUPED_COUNTS) if grouped else 1, splits=sp, **kw)
+
+
+def engine_cases():
+    for sh, form, sp in ENGINE:
+        kernel, args, kw = engine_case(sh, form, sp)
+        yield f"engine/{sh}/{form}/{sp}", None, None, kernel, args, kw
+    for kernel, kern, gc, ga, sc in INSTANCES:
+        args, kw = instance_case(kern, gc, ga, sc)
+        yield f"instance/{kern}/{gc}{ga}{sc}", KERNELS[kern][3], KERNELS[kern][4], kernel, args, kw
+
+
+@pytest.mark.parametrize("sh,form,sp", ENGINE)
+def test_wgrad_as_the_engine_launches(ops, sh, form, sp):
+    kernel, (dtype, M, N, K), kw = engine_case(sh, form, sp)
+    grouped = kw.pop("grouped", False)
+    gc, ga, sc = kw.pop("gc", False), kw.pop("ga", False), kw.pop("sc", False)
+    c_div, a_div = kw.pop("c_div", 1), kw.pop("a_div", 1)
+    c_idx, c_scale, a_idx = _gathers(M, gc, ga, sc, c_div, a_div, seed=6)
+    assert run(ops, dtype, M, N, K, kernel=kernel, counts=GROUPED_COUNTS if grouped else None, c_idx=c_idx, c_div=c_div, c_scale=c_scale,
+               a_idx=a_idx, a_div=a_div, tag=f"engine/{sh}/{form}/{sp}", **kw) < 1
+
+
+def cases():
+    """every run() call of this module's tables as (case id, wgrad_set_dma, wgrad_set_big, stated kernel, plan_args positional,
+    keyword): what the CPU test pins and the engine census is compared with"""
+    for kern, (dtype, N, K, dma, big, want_db, kernel) in KERNELS.items():
+        for sp in SPLITS:
+            yield f"{kern}/{sp}", dma, big, plain_kernel(kern, sp), (dtype, 333, N, K), dict(splits=sp, want_db=want_db)
+    G, M = len(GROUPED_COUNTS), sum(GROUPED_COUNTS) + 19
+    for kern in GROUPED_KERNELS:
+        dtype, N, K, dma, big, _, kernel = KERNELS[kern]
+        for sp in GROUPED_SPLITS:
+            yield (f"grouped/{kern}/{sp}", dma, big, scaled_kernel(kern), (dtype, M, N, K),
+                   dict(G=G, grouped=True, splits=sp, gc=True, c_div=2, sc=True, ga=True, a_div=2))
+            yield f"grouped/{kern}/{sp}/beta1", dma, big, kernel, (dtype, M, N, K), dict(G=G, grouped=True, splits=sp, ga=True, a_div=2)
+    for G in (65, 96):
+        _, M = many_groups_counts(G)
+        for kern in ("staged_f16", "dma_f16"):
+            dtype, N, K, dma, big, _, kernel = KERNELS[kern]
+            for sp in (1, 2):
+                yield f"G{G}/{kern}/{sp}", dma, big, kernel, (dtype, M, 128, 64), dict(G=G, grouped=True, splits=sp)
+    yield from engine_cases()
+
+
+def case_signatures(ops):
+    """{case id: signature} from dummy structs under each case's knobs.  Host only"""
+    out = {}
+    for cid, dma, big, kernel, args, kw in cases():
+        with knobs(ops, dma, big):
+            out[cid] = ls.wgrad_signature(ops, plan_args(ops, *args, **kw))
+    return out
 
 
 def test_wgrad_queue_ride_along(ops):

@@ -40,6 +40,21 @@ def rnd(*shape, seed=0, dtype=torch.float16):
     return torch.randn(*shape, generator=g).to(dtype).to(dev())
 
 
+def case_signatures(ops):
+    """{case id: launch signature (launch_signature.wgrad_multi_signature)} of the batches the tests below launch, from dummy
+    argument structs: what tests/test_engine_launch_census_gpu.py compares the engine's m3_wgrad_multi launches with"""
+    import launch_signature as ls
+    out = {}
+    for dtype in DTYPES:
+        for cid, shapes, bias in (("block", BLOCK, [True, True, False, True]), ("small", SMALL, [True] * len(SMALL))):
+            a = ops.WgradMultiArgs()
+            a.dtype, a.n = ops.dt_code(dtype), len(shapes)
+            for j, (N, K) in enumerate(shapes):
+                a.prob[j].N, a.prob[j].K, a.prob[j].db = N, K, ls.DUMMY if bias[j] else None
+            out[f"{cid}/{dtype}"] = ls.wgrad_multi_signature(ops, a)
+    return out
+
+
 _CASES = {}
 
 
