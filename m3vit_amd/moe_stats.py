@@ -6,8 +6,11 @@ from __future__ import annotations
 
 import struct
 
-HDR = 8                       # M3_MOE_STATS_HIST: four-byte words before the histogram
-(ENTROPY_SUM, TOP1_SUM, CLEAN_STD, NORM_RATIO, LOAD_CV, M_SUMSQ, H_SUMSQ, TOKENS) = range(8)
+# the record's word indices, from include/m3vit_hip.h; HDR: four-byte words before the histogram
+from ._lib import (M3_MOE_STATS_CLEAN_STD as CLEAN_STD, M3_MOE_STATS_ENTROPY_SUM as ENTROPY_SUM,  # noqa: F401
+                   M3_MOE_STATS_H_SUMSQ as H_SUMSQ, M3_MOE_STATS_HIST as HDR, M3_MOE_STATS_LOAD_CV as LOAD_CV,
+                   M3_MOE_STATS_M_SUMSQ as M_SUMSQ, M3_MOE_STATS_NORM_RATIO as NORM_RATIO, M3_MOE_STATS_TOKENS as TOKENS,
+                   M3_MOE_STATS_TOP1_SUM as TOP1_SUM)
 
 
 def record_words(E: int) -> int:

@@ -353,32 +353,32 @@ def gemm_nt(A, B, C, *, M=None, bias=None, act=M3_ACT_NONE, pre_out=None, gelu_g
     N, K = B.shape[-2], B.shape[-1]
     a = GemmArgs()
     a.A = A.data_ptr(); a.lda = A.stride(0)
-    a.a_row_idx = a_row_idx.data_ptr() if a_row_idx is not None else None
+    a.a_row_idx = _p(a_row_idx)
     a.a_row_div = a_row_div
     a.B = B.data_ptr(); a.ldb = B.stride(-2)
     a.C = C.data_ptr(); a.ldc = C.stride(0); a.c_dtype = dt_code(C.dtype)
-    a.c_row_idx = c_row_idx.data_ptr() if c_row_idx is not None else None
-    a.bias = bias.data_ptr() if bias is not None else None
-    a.pre_out = pre_out.data_ptr() if pre_out is not None else None
+    a.c_row_idx = _p(c_row_idx)
+    a.bias = _p(bias)
+    a.pre_out = _p(pre_out)
     a.ld_pre = pre_out.stride(0) if pre_out is not None else 0
-    a.gelu_grad_pre = gelu_grad_pre.data_ptr() if gelu_grad_pre is not None else None
+    a.gelu_grad_pre = _p(gelu_grad_pre)
     a.ld_gpre = gelu_grad_pre.stride(0) if gelu_grad_pre is not None else 0
-    a.residual = residual.data_ptr() if residual is not None else None
+    a.residual = _p(residual)
     a.ld_res = residual.stride(0) if residual is not None else 0
     a.act = act
     if row_scale is not None:
         _req(row_scale, torch.float32, "row_scale")
-    a.row_scale = row_scale.data_ptr() if row_scale is not None else None
+    a.row_scale = _p(row_scale)
     a.row_scale_div = row_scale_div
     if row_scale_idx is not None:
         _req(row_scale_idx, torch.int32, "row_scale_idx")
         assert row_scale is not None
-    a.row_scale_idx = row_scale_idx.data_ptr() if row_scale_idx is not None else None
+    a.row_scale_idx = _p(row_scale_idx)
     if M is None:
         M = a_row_idx.numel() if a_row_idx is not None else A.shape[0]
     a.M = M; a.N = N; a.K = K; a.G = G
-    a.group_offsets = group_offsets.data_ptr() if group_offsets is not None else None
-    a.tile_starts = tile_starts.data_ptr() if tile_starts is not None else None
+    a.group_offsets = _p(group_offsets)
+    a.tile_starts = _p(tile_starts)
     a.dtype = dt_code(A.dtype)
     if bias is not None:
         _req(bias, torch.float32, "bias")
@@ -510,17 +510,17 @@ def wgrad_tn(dC, A, dW, *, M=None, beta=0, splits=None, ws=None, c_row_idx=None,
         ws = torch.empty(max(p.ws_elems, 4), dtype=torch.float32, device=dW.device)
     a = WgradArgs()
     a.dC = dC.data_ptr(); a.lddc = dC.stride(0)
-    a.c_row_idx = c_row_idx.data_ptr() if c_row_idx is not None else None
+    a.c_row_idx = _p(c_row_idx)
     a.c_row_div = c_row_div
     if c_row_scale is not None:
         _req(c_row_scale, torch.float32, "c_row_scale")
         assert c_row_idx is not None
-    a.c_row_scale = c_row_scale.data_ptr() if c_row_scale is not None else None
+    a.c_row_scale = _p(c_row_scale)
     a.A = A.data_ptr(); a.lda = A.stride(0)
-    a.a_row_idx = a_row_idx.data_ptr() if a_row_idx is not None else None
+    a.a_row_idx = _p(a_row_idx)
     a.a_row_div = a_row_div
     a.M = M; a.N = N; a.K = K; a.G = G
-    a.group_offsets = group_offsets.data_ptr() if group_offsets is not None else None
+    a.group_offsets = _p(group_offsets)
     a.splits = p.splits; a.chunk_rows = p.chunk_rows; a.units = p.units
     a.ws = ws.data_ptr()
     a.dtype = dt_code(dC.dtype)
@@ -528,12 +528,12 @@ def wgrad_tn(dC, A, dW, *, M=None, beta=0, splits=None, ws=None, c_row_idx=None,
         _req(db, torch.float32, "db")
     if p.direct:
         a.direct_dW = dW.data_ptr(); a.direct_beta = 1 if beta else 0
-        a.direct_db = db.data_ptr() if db is not None else None
+        a.direct_db = _p(db)
         a.direct_beta_db = 1 if bdb else 0
     else:
         # the reduction of this call's slabs; both slab kinds in one launch where db and the bias slabs are 16-byte aligned
         bias_ws = ws[p.units * N * K:] if db is not None else None
-        a.bias_ws = bias_ws.data_ptr() if db is not None else None
+        a.bias_ws = _p(bias_ws)
         fuse = db is not None and db.data_ptr() % 16 == 0 and bias_ws.data_ptr() % 16 == 0
         assert db is None or fuse or queue is None, "queued wgrad: db and the bias slabs must be 16-byte aligned"
         assert db is None or fuse or not p.chunk_rows, "balanced grouped wgrad: db and the bias slabs must be 16-byte aligned"
@@ -800,12 +800,12 @@ class LnGradTable:
     """device-resident (dgamma, dbeta) pointer pairs of a model's LayerNorms, in workspace-slot order"""
 
     def __init__(self, pairs, device):
-        import struct
         self.keep = pairs
-        for g, b in pairs:
+        arr = (_lib.LnParamGrads * len(pairs))()
+        for d, (g, b) in zip(arr, pairs):
             _req(g, torch.float32, "dgamma"); _req(b, torch.float32, "dbeta")
-        raw = b"".join(struct.pack("QQ", g.data_ptr(), b.data_ptr()) for g, b in pairs)
-        self.table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
+            d.dgamma, d.dbeta = g.data_ptr(), b.data_ptr()
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
         self.n = len(pairs)
 
 
@@ -883,8 +883,8 @@ class CastPlan:
                     assert o.numel() == src.numel()
             assert dst is not None or dst_t is not None
             d.src, d.G, d.rows, d.cols, d.tile_start = src.data_ptr(), G, rows, cols, t0
-            d.dst = dst.data_ptr() if dst is not None else None
-            d.dst_t = dst_t.data_ptr() if dst_t is not None else None
+            d.dst = _p(dst)
+            d.dst_t = _p(dst_t)
             t0 += G * ((rows + 31) // 32) * ((cols + 31) // 32)
             self.keep += [src, dst, dst_t]
         self.n, self.total, self.dtype = len(jobs), t0, dst_dtype

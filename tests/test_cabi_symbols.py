@@ -1,7 +1,11 @@
-"""CPU: the C-ABI library loads and exports every symbol include/m3vit_hip.h declares
+"""CPU: the C-ABI library loads and exports every symbol include/m3vit_hip.h declares, and the ctypes bindings that
+m3vit_amd._lib derives from the header's text agree with what a C++ compiler makes of the same header
 (no compute calls without a GPU)."""
+import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -28,6 +32,92 @@ def test_header_symbols_all_bound_and_exported():
     assert L.m3_version() >= 100
     assert L.m3_gate_num_blocks(25216) == 394
     assert L.m3_route_ws_elems(100864, 16) > 0
+
+
+def _header_text():
+    txt = open(os.path.join(ROOT, "include", "m3vit_hip.h")).read()
+    return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+
+
+def _kind(t):
+    """what the compiled probe prints for a type: p(ointer) / f(loat) / i(nteger) and the byte size"""
+    if issubclass(t, (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)):
+        return f"p{ctypes.sizeof(t)}"
+    return ("f" if t in (ctypes.c_float, ctypes.c_double) else "i") + str(ctypes.sizeof(t))
+
+
+def test_derived_bindings_match_the_compiler(tmp_path):
+    """sizeof and every field's offset and size of every struct, the value of every M3_* constant, and the parameter count
+    and each parameter's and the return type's kind and size of every entry point: as a host C++ compiler sees the header
+    against the ctypes tables read from its text.  A dropped argument, an int for an int64_t, a float for an int, a field
+    missing or out of order, a renumbered constant: each shows here, on the CPU, instead of as a stray device write."""
+    from m3vit_amd import _lib
+    txt = _header_text()                                      # the reader skipped nothing: independent counts
+    assert len(_lib.CONSTANTS) == len(re.findall(r"^\s*#\s*define\s+M3_", txt, flags=re.M)) >= 83
+    assert len(_lib.STRUCTS) == len(re.findall(r"\btypedef\s+struct\b", txt)) >= 17
+    src = ["#include <cstddef>", "#include <cstdio>", "#include <type_traits>", '#include "m3vit_hip.h"',
+           "template <class T> void k() { std::printf(\" %c%zu\", std::is_pointer<T>::value ? 'p' : "
+           "std::is_floating_point<T>::value ? 'f' : 'i', sizeof(T)); }",
+           "template <class F> struct sig;",               # over the function's TYPE: the probe links against nothing
+           "template <class R, class... A> struct sig<R (*)(A...)> { static void print(const char *n) "
+           "{ std::printf(\"F %s %zu\", n, sizeof...(A)); k<R>(); (k<A>(), ...); std::printf(\"\\n\"); } };",
+           "int main() {"]
+    want = []
+    for name, val in _lib.CONSTANTS.items():
+        src.append(f'  std::printf("C {name} %lld\\n", (long long)({name}));')
+        want.append(f"C {name} {val}")
+    for name, cls in _lib.STRUCTS.items():
+        fields = [f for f, _ in cls._fields_]
+        src.append(f'  std::printf("S {name} %zu' + " %zu:%zu" * len(fields) + f'\\n", sizeof({name})'
+                   + "".join(f", offsetof({name}, {f}), sizeof({name}::{f})" for f in fields) + ");")
+        want.append(f"S {name} {ctypes.sizeof(cls)}" + "".join(f" {getattr(cls, f).offset}:{getattr(cls, f).size}" for f in fields))
+    for name, (res, args) in _lib.SIGNATURES.items():
+        src.append(f'  sig<decltype(&{name})>::print("{name}");')
+        want.append(f"F {name} {len(args)} " + " ".join(_kind(t) for t in [res] + args))
+    src += ["  return 0;", "}"]
+    (tmp_path / "probe.cpp").write_text("\n".join(src) + "\n")
+    cxx = [shutil.which("c++")] if shutil.which("c++") else [shutil.which("hipcc") or "/opt/rocm/bin/hipcc", "-x", "c++"]
+    subprocess.check_call(cxx + ["-std=c++17", "-I", os.path.join(ROOT, "include"), str(tmp_path / "probe.cpp"),
+                                 "-o", str(tmp_path / "probe")])      # host code only: nothing is compiled for a device
+    got = subprocess.check_output([str(tmp_path / "probe")], text=True).splitlines()
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        assert g == w, f"compiler: {g!r}  ctypes: {w!r}"
+
+
+def test_reader_type_rules():
+    """one entry point of each kind the header's reader has a rule for"""
+    from ctypes import POINTER, c_char_p, c_double, c_int, c_int32, c_void_p
+    from m3vit_amd import _lib
+    S = _lib.SIGNATURES
+    assert S["m3_last_error"] == (c_char_p, [])
+    assert S["m3_loss_bce_fwd"][1][9] is c_double
+    assert S["m3_ep_init"][1][3] is POINTER(c_int)
+    assert S["m3_cast_batch"][1][0] is c_void_p                                    # descs_dev: a device address
+    assert S["m3_wgrad_multi"][1][0] is POINTER(_lib.WgradMultiArgs)               # a struct the host fills
+    assert S["m3_gemm_plan"][1] == [POINTER(_lib.GemmArgs), POINTER(_lib.GemmPlan)]
+    N = dict(_lib.WgradMultiShape._fields_)["N"]
+    assert issubclass(N, ctypes.Array) and N._type_ is c_int32 and N._length_ == _lib.M3_WGRAD_MULTI_MAX == _lib.WGRAD_MULTI_MAX
+    assert _lib.WgradMultiArgs is _lib.STRUCTS["m3_wgrad_multi_args"] and _lib.LnParamGrads is _lib.STRUCTS["m3_ln_param_grads"]
+    assert dict(_lib.WgradMultiArgs._fields_)["prob"]._type_ is _lib.WgradProblem  # nested struct array
+    assert dict(_lib.WgradArgs._fields_)["prev"] is POINTER(_lib.WgradReduceDesc)  # pointer to another struct
+
+
+@pytest.mark.parametrize("text, named", [
+    ("int m3_ok(int a);\nint m3_broken(int a, float);\n", "m3_broken(int a, float)"),          # a parameter without a name
+    ("int m3_ok(int a);\nint m3_odd(const uint8_t *p, int n);\n", "m3_odd(const uint8_t *p, int n)"),   # an unknown type
+    ("typedef struct { int32_t a; unsigned b; } m3_t;\n", "unsigned b"),                       # ... in a struct
+    ("#define M3_X 1u\n", "#define M3_X 1u"),                                                  # not a plain integer
+    ("typedef struct { int32_t a[M3_NOPE]; } m3_t;\n", "int32_t a[M3_NOPE]"),                  # an unknown dimension
+    ("int m3_a(int a)\nint m3_b(void);\n", "int m3_a(int a) int m3_b(void)"),                  # a lost semicolon
+])
+def test_reader_fails_loudly(text, named):
+    """what the reader does not understand raises and names the text: nothing is skipped"""
+    from m3vit_amd import _lib
+    assert _lib.read_header("int m3_ok(int a);\n")[2] == {"m3_ok": (ctypes.c_int, [ctypes.c_int])}
+    with pytest.raises(_lib.M3Error) as e:
+        _lib.read_header(text)
+    assert named in str(e.value)
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
