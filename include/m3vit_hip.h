@@ -800,6 +800,65 @@ int m3_meter_normals_update(const void *pred, int dtype, const float *label, int
 int m3_meter_sal_update(const void *pred, int dtype, const float *label, int B, int H, int W, void *ws, void *state,
                         void *stream);
 
+/* ------------------------------------------------------------- pretraining recipe
+ * What the ImageNet pretraining trainer runs around the model and the optimizer (pretrain/train.py:461-471,498,536,877-905):
+ * batch mixing, the soft-target criterion, the evaluation sums and the weight EMA.  Nothing is read back to the host, no float
+ * atomics, the same bits from run to run.
+ *
+ * m3_mix_batch: Mixup / CutMix of x [B,C,H,W] (fp32, NCHW) with its batch-reversed self (the mixup_fn call of
+ * pretrain/engine/train_one_epoch.py:32-33): sample i is paired with j = B-1-i, B even.  lam f32 [B], box i32 [B,4] = yl, yh,
+ * xl, xh per sample (DEVICE).  Empty box (yl == yh or xl == xh): out_i = lam_i x_i + (1 - lam_i) x_j, lam 1 and 0 bit copies;
+ * else out_i = x_j inside the box and x_i outside, bit copies.  Both members of a pair are read before either is written:
+ * out == x is valid (out_dtype M3_F32 then), and lam_i != lam_j is.  Out of place out may be M3_F16 / M3_BF16 (one rounding).
+ * 16-byte accesses where x and out are 16-byte aligned and W % 4 == 0.
+ * m3_mix_target: the dense soft target [B,C] f32 of the same pairing: t_i = lam_i s(y_i) + (1 - lam_i) s(y_j), s(y) = off =
+ * smoothing / C everywhere and 1 - smoothing + off at y.  label int64 [B]; a label outside [0, C) adds only the off floor and
+ * is counted in *n_bad (DEVICE int32, written). */
+int m3_mix_batch(const float *x, int B, int C, int H, int W, const float *lam, const int32_t *box, void *out, int out_dtype,
+                 void *stream);
+int m3_mix_target(const int64_t *label, const float *lam, int B, int C, double smoothing, float *target, int32_t *n_bad,
+                  void *stream);
+/* Cross-entropy of row-major logits [B,C] (M3_F32 / M3_F16 / M3_BF16), 1 <= C <= M3_SOFTCE_MAX_C, B*C < 2^31 - 2^20, against
+ * EXACTLY ONE of (pretrain/models/losses.py:77-83: SoftTargetCrossEntropy, LabelSmoothingCrossEntropy, nn.CrossEntropyLoss):
+ *   target f32 [B,C]: loss = (1/B) sum_i [ S_i lse(x_i) - sum_c t_ic x_ic ], S_i = sum_c t_ic (= sum(-t log_softmax(x)); right
+ *     for rows that do not sum to 1 or are all zero); smoothing is not read;
+ *   label int64 [B]:  loss = (1/B) sum_i [ lse(x_i) - (1 - s) x_i[y_i] - (s / C) sum_c x_ic ], s = smoothing (0: plain cross-
+ *     entropy, pretrain/engine/evaluate.py:12,29).  A label outside [0, C) indexes nothing (its row adds lse - (s / C) sum x)
+ *     and is counted in the record's N_BAD.
+ * lse f32 [B] (running maximum: finite at |x| = 6e4) and, for a dense target, tsum f32 [B] = S_i are written by the forward and
+ * read by the backward (tsum may be NULL with labels).  ws: m3_softce_ws_elems(B) floats, no initialisation.  record: the
+ * M3_LOSS_REC_WORDS words of the dense-prediction losses (VALUE the loss, COEF 1 / B, N_VALID B, N_BAD).  Forward: one
+ * workgroup per row, then one workgroup that adds the rows in order in double.
+ * Backward: dlogits (the logits' dtype) = (softmax(x_i)_c S_i - t_ic) * COEF * *grad_out (DEVICE f32: a loss scale needs no
+ * host read); with labels t is the implied target and S_i = 1.  16-byte accesses where C % 4 == 0 and logits / target / dlogits
+ * are 16-byte aligned. */
+#define M3_SOFTCE_MAX_C 65536
+int64_t m3_softce_ws_elems(int B);
+int m3_loss_softce_fwd(const void *logits, int dtype, const float *target, const int64_t *label, double smoothing, int B,
+                       int C, float *lse, float *tsum, float *ws, void *record, void *stream);
+int m3_loss_softce_bwd(const void *logits, int dtype, const float *target, const int64_t *label, double smoothing,
+                       const float *lse, const float *tsum, const void *record, const float *grad_out, int B, int C,
+                       void *dlogits, void *stream);
+/* One batch of the evaluation loop (pretrain/engine/evaluate.py:29-37) ADDED to state, M3_CLS_EVAL_WORDS 8-byte words: f64
+ * LOSS_SUM, CORRECT1, CORRECT5, COUNT - the vector evaluate.py:44-50 all-reduces - then int64 N_BAD.  Per row the plain cross-
+ * entropy lse - x[y] and rank = #{c : x_c > x_y} + #{c < y : x_c == x_y} (ties to the lower index; a NaN logit beats every
+ * number and the first NaN wins); CORRECT1 += [rank < 1], CORRECT5 += [rank < min(5, C)].  A label outside [0, C) counts in
+ * COUNT and N_BAD, adds lse to LOSS_SUM and is never correct.  ws: m3_cls_eval_ws_elems(B) four-byte words. */
+#define M3_CLS_EVAL_LOSS_SUM 0
+#define M3_CLS_EVAL_CORRECT1 1
+#define M3_CLS_EVAL_CORRECT5 2
+#define M3_CLS_EVAL_COUNT 3
+#define M3_CLS_EVAL_N_BAD 4
+#define M3_CLS_EVAL_WORDS 5
+int64_t m3_cls_eval_ws_elems(int B);
+int m3_cls_eval_update(const void *logits, int dtype, const int64_t *label, int B, int C, void *ws, void *state, void *stream);
+/* The weight EMA behind every step (pretrain/engine/train_one_epoch.py:62-63): ema = decay ema + one_minus_decay src for all
+ * tensors of an m3_optim_desc table in one launch - p the fp32 shadow, g the fp32 source, n, chunk_start and vec_ok as for
+ * m3_optim_step; m, v and group are not read.  Both factors are formed by the host in double.  decay 1 writes nothing, decay 0
+ * copies the source's bits. */
+int m3_ema_update(const m3_optim_desc *descs_dev, int n_desc, int total_chunks, float decay, float one_minus_decay,
+                  void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,8 @@ accumulation, fp32 master weights) - the custom autograd Functions pick their dt
 surrounding `torch.autocast` context is harmless and not needed.
 
 Out of scope here as in the reference's own hot path: distillation token / head_dist, DeiT warm start
-(network fetch), mixup, EMA."""
+(network fetch).  Mixup / CutMix, the soft-target criteria, the EMA and the evaluation sums of the same trainer
+are in m3vit_amd/pretrain.py."""
 from dataclasses import dataclass
 import math
 

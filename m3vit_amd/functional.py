@@ -376,6 +376,27 @@ class SoftmaxCrossEntropyFn(torch.autograd.Function):
         return ops.loss_ce_bwd(p, lab, lse, record, _upstream(g)), None
 
 
+class SoftCrossEntropyFn(torch.autograd.Function):
+    """pretrain/models/losses.py:77-83: the cross-entropy of [B, C] logits against a dense float32 target [B, C]
+    (SoftTargetCrossEntropy) or int64 labels [B] with a smoothing scalar (LabelSmoothingCrossEntropy; 0: nn.CrossEntropyLoss)
+    over csrc/pretrain.hip's pair; saves the rows' log-sum-exp (and target sums), so the backward is a single pass."""
+
+    @staticmethod
+    def forward(ctx, logits, target, smoothing):
+        x = logits.contiguous()
+        tgt = target.detach().contiguous()
+        record, lse, tsum = ops.loss_softce_fwd(x, tgt, smoothing)
+        ctx.save_for_backward(x, tgt, record, lse, tsum)
+        ctx.smoothing = smoothing
+        ctx.mark_non_differentiable(record)
+        return _loss_value(record), record
+
+    @staticmethod
+    def backward(ctx, g, _g_record):
+        x, tgt, record, lse, tsum = ctx.saved_tensors
+        return ops.loss_softce_bwd(x, tgt, lse, tsum, record, _upstream(g), ctx.smoothing), None, None
+
+
 class MaskedL1Fn(torch.autograd.Function):
     """losses/loss_functions.py:126-140 (DepthLoss('l1'))"""
 

@@ -1291,6 +1291,181 @@ def meter_sal_update(pred, label, *, ws=None, state=None):
     return state
 
 
+# ------------------------------------------------------------------------------- pretraining recipe (csrc/pretrain.hip)
+CLS_EVAL_WORDS = _lib.M3_CLS_EVAL_WORDS
+
+
+def _mix_lam(lam, B):
+    if B < 2 or B % 2:
+        raise _lib.M3Error(f"mixing pairs sample i with B-1-i: the batch must be even and non-empty, got B = {B}")
+    _req(lam, torch.float32, "lam", numel=B)
+
+
+def mix_batch(x, lam, box, *, out=None, out_dtype=None):
+    """Mixup / CutMix of x [B,C,H,W] (float32, contiguous) with its batch-reversed self (m3_mix_batch): lam float32 [B], box
+    int32 [B,4] = yl, yh, xl, xh per sample, both on the device; an empty box means Mixup for that sample.  out=None: in place
+    (returns x), or with out_dtype a new tensor of that activation dtype; out=x is in place too.  Nothing is read back."""
+    B, C, H, W = _dims(x, 4, "x")
+    _req(x, torch.float32, "x")
+    _mix_lam(lam, B)
+    _req(box, torch.int32, "box", numel=4 * B)
+    if out is None:
+        out = x if out_dtype in (None, torch.float32) else torch.empty_like(x, dtype=out_dtype)
+    _act(out, "out", numel=x.numel())
+    if out.shape != x.shape:
+        raise _lib.M3Error(f"out must have x's shape {tuple(x.shape)}, got {tuple(out.shape)}")
+    if out.data_ptr() == x.data_ptr() and out.dtype != torch.float32:
+        raise _lib.M3Error("in place only with a float32 output")
+    check(lib().m3_mix_batch(_p(x), B, C, H, W, _p(lam), _p(box), _p(out), dt_code(out.dtype), _stream()), "m3_mix_batch")
+    return out
+
+
+def mix_target(label, lam, num_classes, smoothing=0.0, *, out=None, n_bad=None):
+    """The dense soft target float32 [B, num_classes] of mix_batch's pairing (m3_mix_target): label int64 [B], lam float32 [B].
+    Returns (target, n_bad): n_bad a 1-element int32 device tensor, the labels outside [0, num_classes)."""
+    if not isinstance(label, torch.Tensor) or label.dim() != 1:
+        raise _lib.M3Error("label must be a 1-d int64 tensor")
+    B, C = label.numel(), int(num_classes)
+    _req(label, torch.int64, "label")
+    _mix_lam(lam, B)
+    if C < 1 or B * C >= 2 ** 31 - 2 ** 20:
+        raise _lib.M3Error(f"num_classes = {C} with B = {B}: need C >= 1 and B * C < 2^31 - 2^20")
+    if not 0.0 <= float(smoothing) <= 1.0:
+        raise _lib.M3Error(f"smoothing must be in [0, 1], got {smoothing}")
+    if out is None:
+        out = torch.empty(B, C, dtype=torch.float32, device=label.device)
+    _req(out, torch.float32, "out", numel=B * C)
+    if n_bad is None:
+        n_bad = torch.empty(1, dtype=torch.int32, device=label.device)
+    _req(n_bad, torch.int32, "n_bad", numel=1)
+    check(lib().m3_mix_target(_p(label), _p(lam), B, C, float(smoothing), _p(out), _p(n_bad), _stream()), "m3_mix_target")
+    return out, n_bad
+
+
+def softce_ws_elems(B: int) -> int:
+    return int(lib().m3_softce_ws_elems(B))
+
+
+def _softce_args(logits, target, smoothing):
+    """(B, C, dense target or None, labels or None) of a soft-target / label-smoothing cross-entropy call"""
+    B, C = _dims(logits, 2, "logits")
+    _act(logits, "logits")
+    if B < 1 or not 1 <= C <= _lib.M3_SOFTCE_MAX_C:
+        raise _lib.M3Error(f"logits must be [B >= 1, 1 <= C <= {_lib.M3_SOFTCE_MAX_C}], got {tuple(logits.shape)}")
+    if B * C >= 2 ** 31 - 2 ** 20:
+        raise _lib.M3Error(f"{B * C} logits: the kernels index with 32 bits")
+    if not isinstance(target, torch.Tensor):
+        raise _lib.M3Error(f"target must be a tensor, got {type(target).__name__}")
+    if not 0.0 <= float(smoothing) <= 1.0:
+        raise _lib.M3Error(f"smoothing must be in [0, 1], got {smoothing}")
+    if target.dtype == torch.int64:
+        if target.dim() != 1:
+            raise _lib.M3Error(f"hard labels must be int64 [B], got shape {tuple(target.shape)}")
+        _req(target, torch.int64, "target", numel=B)
+        return B, C, None, target
+    if tuple(target.shape) != (B, C):
+        raise _lib.M3Error(f"a dense target must be float32 of the logits' shape {(B, C)}, got {target.dtype} {tuple(target.shape)}")
+    _req(target, torch.float32, "target", numel=B * C)
+    return B, C, target, None
+
+
+def loss_softce_fwd(logits, target, smoothing=0.0, *, lse=None, tsum=None, ws=None, record=None):
+    """Cross-entropy of logits [B, C] (fp32 / fp16 / bf16) against a dense float32 target [B, C] or int64 labels [B] with a
+    smoothing scalar (m3_loss_softce_fwd).  Returns (record, lse, tsum): the int32 record of the dense-prediction losses
+    (loss value, 1 / B, bad labels), the rows' log-sum-exp and - for a dense target - their target sums, both for the
+    backward.  Nothing is read back."""
+    B, C, dense, lab = _softce_args(logits, target, smoothing)
+    dev = logits.device
+    need = softce_ws_elems(B)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.float32, device=dev)
+    _req(ws, torch.float32, "ws", min_numel=need)
+    if record is None:
+        record = torch.empty(LOSS_REC_WORDS, dtype=torch.int32, device=dev)
+    _req(record, torch.int32, "record", numel=LOSS_REC_WORDS)
+    if lse is None:
+        lse = torch.empty(B, dtype=torch.float32, device=dev)
+    _req(lse, torch.float32, "lse", numel=B)
+    if dense is not None and tsum is None:
+        tsum = torch.empty(B, dtype=torch.float32, device=dev)
+    if tsum is not None:
+        _req(tsum, torch.float32, "tsum", numel=B)
+    check(lib().m3_loss_softce_fwd(_p(logits), dt_code(logits.dtype), _p(dense), _p(lab), float(smoothing), B, C, _p(lse),
+                                   _p(tsum), _p(ws), _p(record), _stream()), "m3_loss_softce_fwd")
+    return record, lse, tsum
+
+
+def loss_softce_bwd(logits, target, lse, tsum, record, grad_out, smoothing=0.0, *, dlogits=None):
+    """d logits of loss_softce_fwd, scaled by the 1-element float32 GPU tensor grad_out (read on the device); in the logits'
+    dtype"""
+    B, C, dense, lab = _softce_args(logits, target, smoothing)
+    _req(lse, torch.float32, "lse", numel=B)
+    if dense is not None:
+        _req(tsum, torch.float32, "tsum", numel=B)
+    _req(record, torch.int32, "record", numel=LOSS_REC_WORDS)
+    _req(grad_out, torch.float32, "grad_out", numel=1)
+    if dlogits is None:
+        dlogits = torch.empty_like(logits)
+    _req(dlogits, logits.dtype, "dlogits", numel=B * C)
+    check(lib().m3_loss_softce_bwd(_p(logits), dt_code(logits.dtype), _p(dense), _p(lab), float(smoothing), _p(lse),
+                                   _p(tsum if dense is not None else None), _p(record), _p(grad_out), B, C, _p(dlogits),
+                                   _stream()), "m3_loss_softce_bwd")
+    return dlogits
+
+
+def cls_eval_ws_elems(B: int) -> int:
+    return int(lib().m3_cls_eval_ws_elems(B))
+
+
+def cls_eval_state(device) -> torch.Tensor:
+    """a zeroed evaluation state: int64 words; the first four read through .view(torch.float64) are loss_sum, correct1,
+    correct5, count, the fifth counts the bad labels (layout: include/m3vit_hip.h, M3_CLS_EVAL_*)"""
+    return torch.zeros(CLS_EVAL_WORDS, dtype=torch.int64, device=device)
+
+
+def cls_eval_update(logits, label, *, ws=None, state=None):
+    """One batch of classification evaluation ADDED to state (m3_cls_eval_update): logits [B, C] fp32 / fp16 / bf16, label
+    int64 [B].  Returns state.  Nothing is read back."""
+    B, C, _, lab = _softce_args(logits, label, 0.0)
+    if lab is None:
+        raise _lib.M3Error("label must be int64 [B]")
+    need = cls_eval_ws_elems(B)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.int32, device=logits.device)
+    _req(ws, torch.int32, "ws", min_numel=need)
+    if state is None:
+        state = cls_eval_state(logits.device)
+    _req(state, torch.int64, "state", numel=CLS_EVAL_WORDS)
+    check(lib().m3_cls_eval_update(_p(logits), dt_code(logits.dtype), _p(lab), B, C, _p(ws), _p(state), _stream()),
+          "m3_cls_eval_update")
+    return state
+
+
+def ema_table(pairs):
+    """The device-resident descriptor table of m3_ema_update: pairs = [(ema, src)] float32 contiguous GPU tensors of equal
+    element counts.  Returns (table uint8 tensor, n_desc, total_chunks); the caller keeps the tensors alive."""
+    if not pairs:
+        raise _lib.M3Error("ema_table needs at least one (ema, src) pair")
+    rows = []
+    for e, s in pairs:
+        n = _req(e, torch.float32, "ema tensor").numel()
+        _req(s, torch.float32, "source tensor", n)
+        if e.device != s.device:
+            raise _lib.M3Error("an ema tensor and its source must live on the same device")
+        rows.append((e.data_ptr(), s.data_ptr(), 0, 0, n, 0))
+    arr, total = optim_table(rows)                   # m, v null: p and g alone decide vec_ok
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(pairs[0][0].device), len(rows), total
+
+
+def ema_update(table, n_desc, total_chunks, decay):
+    """ema = decay * ema + (1 - decay) * src for every pair of an ema_table in one launch; both factors formed here in double"""
+    d = float(decay)
+    if not 0.0 <= d <= 1.0:
+        raise _lib.M3Error(f"decay must be in [0, 1], got {decay}")
+    _req(table, torch.uint8, "table", numel=n_desc * ctypes.sizeof(_lib.OptimDesc))
+    check(lib().m3_ema_update(_p(table), int(n_desc), int(total_chunks), d, 1.0 - d, _stream()), "m3_ema_update")
+
+
 def cast_f32(src, dst):
     _req(src, torch.float32, "src"); _act(dst, "dst", src.numel())
     check(lib().m3_cast_f32(_p(src), src.numel(), _p(dst), dt_code(dst.dtype), _stream()), "m3_cast_f32")
