@@ -859,6 +859,50 @@ int m3_cls_eval_update(const void *logits, int dtype, const int64_t *label, int 
 int m3_ema_update(const m3_optim_desc *descs_dev, int n_desc, int total_chunks, float decay, float one_minus_decay,
                   void *stream);
 
+/* ------------------------------------------------------------- dense-prediction augmentation
+ * The per-sample transform chain of the multi-task trainer (utils/common_config.py:583-632: RandomHorizontalFlip, ScaleNRotate,
+ * FixedResize, AddIgnoreRegions, ToTensor, Normalize of data/custom_transforms.py:18-82,88-138,174-191,243-318; the batch
+ * reaches the step at train/train_utils.py:362-368) for every map of a raw batch in ONE launch: flip, warp and resize composed
+ * into one resampling, then the map kind's post-operation, stored NCHW.  Nothing is read back; the same bits from run to run.
+ *
+ * descs: a HOST array of n_maps <= M3_AUG_MAX_MAPS descriptors, passed to the kernel by value.  src [B,H,W,C] ([B,H,W] for
+ * C = 1), contiguous, src_dtype M3_F32 or M3_AUG_U8; dst [B,C,Ho,Wo] contiguous, fp32 (an M3_AUG_IMAGE map: fp32 / fp16 / bf16).
+ * All maps share B, H, W, Ho, Wo and border.  mats: DEVICE f64 [B,6] = a00 a01 a02 a10 a11 a12, the map from an output pixel
+ * (x, y) to source coordinates, u = (a00 x + a01 y) + a02, v = (a10 x + a11 y) + a12, evaluated in double with every product and
+ * sum rounded on its own (no fused multiply-add) in exactly that association.  aux: DEVICE f32 [B,4] = sc, cos(rot), sin(rot),
+ * flip (non-zero: flipped).
+ * mode M3_AUG_NEAREST: the tap (floor(u + 0.5), floor(v + 0.5)), a bit copy.  M3_AUG_LINEAR: x0 = floor(u), t = (float)(u - x0),
+ * weights 1 - t, t.  M3_AUG_CUBIC: taps x0 - 1 .. x0 + 2, the Keys kernel with a = -0.75 (cv2.INTER_CUBIC), weights in fp32 from
+ * t.  t == 0 on an axis gives exactly the weights (1, 0) / (0, 1, 0, 0); a tap of weight zero is not read.  border
+ * M3_AUG_BORDER_ZERO: a tap outside the source is 0 (cv2.warpAffine's default); M3_AUG_BORDER_REPLICATE: its index is clamped
+ * (cv2.resize).  The weighted sum runs in fp32.
+ * kind M3_AUG_IMAGE (C 3): with quantize, q = trunc(clamp(v, 0, 255)) (ToTensor's astype(uint8), clamped where numpy wraps),
+ * then (q / 255 - mean[c]) / std[c].  M3_AUG_LABEL (C 1): nothing more.  M3_AUG_DEPTH (C 1): v / sc, then 0 becomes 255
+ * (custom_transforms.py:77-78,264-266).  M3_AUG_NORMALS (C 3): channel 0 negated when flipped (:188-189), (n0, n1) rotated,
+ * n0' = n0 cos + n1 sin, n1' = n1 cos - n0 sin (:67-73), n / (|n|_2 + 2^-23) (:131-134), and all three channels 255 where
+ * |n|_2 == 0 (:251-256).  The per-sample "no human part anywhere => all 255" rule (:258-262) is not built.
+ * Refused (M3_ERR_ARG, nothing launched): n_maps outside [1, M3_AUG_MAX_MAPS]; B, H, W, Ho, Wo < 1; a C that is not the kind's;
+ * a uint8 label, depth or normals map resampled other than nearest, a 16-bit output of another kind than the image, a
+ * non-positive std; a map of 2^31 - 2^20 elements or more. */
+#define M3_AUG_MAX_MAPS 8
+#define M3_AUG_U8 3
+#define M3_AUG_IMAGE 0
+#define M3_AUG_LABEL 1
+#define M3_AUG_DEPTH 2
+#define M3_AUG_NORMALS 3
+#define M3_AUG_NEAREST 0
+#define M3_AUG_LINEAR 1
+#define M3_AUG_CUBIC 2
+#define M3_AUG_BORDER_ZERO 0
+#define M3_AUG_BORDER_REPLICATE 1
+typedef struct m3_augment_desc {
+  void *src; void *dst;
+  int32_t kind, mode, C, src_dtype, dst_dtype, quantize;
+  float mean[3], std[3];
+} m3_augment_desc;
+int m3_augment_batch(const m3_augment_desc *descs, int n_maps, int B, int H, int W, int Ho, int Wo, int border,
+                     const double *mats, const float *aux, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1466,6 +1466,55 @@ def ema_update(table, n_desc, total_chunks, decay):
     check(lib().m3_ema_update(_p(table), int(n_desc), int(total_chunks), d, 1.0 - d, _stream()), "m3_ema_update")
 
 
+# ------------------------------------------------------------------ dense-prediction augmentation (csrc/augment.hip)
+AUG_KINDS = {"image": _lib.M3_AUG_IMAGE, "label": _lib.M3_AUG_LABEL, "depth": _lib.M3_AUG_DEPTH, "normals": _lib.M3_AUG_NORMALS}
+AUG_MODES = {"nearest": _lib.M3_AUG_NEAREST, "linear": _lib.M3_AUG_LINEAR, "cubic": _lib.M3_AUG_CUBIC}
+AUG_BORDERS = {"zero": _lib.M3_AUG_BORDER_ZERO, "replicate": _lib.M3_AUG_BORDER_REPLICATE}
+_AUG_SRC_DT = {torch.float32: M3_F32, torch.uint8: _lib.M3_AUG_U8}
+
+
+def augment_batch(maps, mats, aux, border="zero"):
+    """Flip, warp, resize and post-process every map of a raw batch in one launch (m3_augment_batch).  maps: a list of
+    (src, dst, kind, mode, quantize, mean, std): src [B,H,W,C] or [B,H,W], float32 or uint8, contiguous; dst [B,C,Ho,Wo]
+    contiguous (float32; an image may be float16 / bfloat16); kind, mode and border by name or code; mean / std: three floats
+    for an image, None otherwise.  All maps share B, H, W, Ho, Wo.  mats float64 [B,6], aux float32 [B,4], both on the device
+    (include/m3vit_hip.h).  What makes no sense (a C that is not the kind's, a cubic class map, more than 8 maps) is refused by
+    the library before anything is launched.  Returns the dst tensors."""
+    if not maps:
+        raise _lib.M3Error("augment_batch needs at least one map")
+    arr = (_lib.AugmentDesc * len(maps))()
+    shape = None
+    for i, (d, (src, dst, kind, mode, quantize, mean, std)) in enumerate(zip(arr, maps)):
+        name = f"map {i}"
+        if not isinstance(src, torch.Tensor) or src.dim() not in (3, 4) or src.dtype not in _AUG_SRC_DT:
+            raise _lib.M3Error(f"{name}: the source must be a float32 or uint8 [B,H,W,C] or [B,H,W] tensor")
+        _req(src, name=name + " source")
+        B, H, W = src.shape[:3]
+        C = src.shape[3] if src.dim() == 4 else 1
+        _dims(dst, 4, name + " output")
+        _act(dst, name + " output")
+        if dst.shape[0] != B or dst.shape[1] != C or dst.device != src.device:
+            raise _lib.M3Error(f"{name}: the output must be [{B}, {C}, Ho, Wo] on the source's device, got {tuple(dst.shape)}")
+        if shape is None:
+            shape = (B, H, W, dst.shape[2], dst.shape[3], src.device)
+        elif shape != (B, H, W, dst.shape[2], dst.shape[3], src.device):
+            raise _lib.M3Error(f"{name}: all maps of one call share B, H, W, Ho, Wo and the device")
+        d.src, d.dst = src.data_ptr(), dst.data_ptr()
+        d.kind = AUG_KINDS[kind] if isinstance(kind, str) else int(kind)
+        d.mode = AUG_MODES[mode] if isinstance(mode, str) else int(mode)
+        d.C, d.src_dtype, d.dst_dtype, d.quantize = C, _AUG_SRC_DT[src.dtype], dt_code(dst.dtype), int(bool(quantize))
+        for c in range(3):
+            d.mean[c], d.std[c] = (float(mean[c]), float(std[c])) if mean is not None else (0.0, 1.0)
+    B, H, W, Ho, Wo, dev = shape
+    _req(mats, torch.float64, "mats", numel=6 * B)
+    _req(aux, torch.float32, "aux", numel=4 * B)
+    if mats.device != dev or aux.device != dev:
+        raise _lib.M3Error("mats and aux must live on the maps' device")
+    check(lib().m3_augment_batch(arr, len(maps), B, H, W, Ho, Wo, AUG_BORDERS[border] if isinstance(border, str) else int(border),
+                                 _p(mats), _p(aux), _stream()), "m3_augment_batch")
+    return [m[1] for m in maps]
+
+
 def cast_f32(src, dst):
     _req(src, torch.float32, "src"); _act(dst, "dst", src.numel())
     check(lib().m3_cast_f32(_p(src), src.numel(), _p(dst), dt_code(dst.dtype), _stream()), "m3_cast_f32")
