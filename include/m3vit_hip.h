@@ -665,6 +665,53 @@ int m3_relu_up2x_fwd(const void *x, int x_dtype, int64_t N, int H, int W, int C,
                      void *stream);
 int m3_relu_up2x_bwd(const void *dy, int dy_dtype, const void *x, int x_dtype, int64_t N, int H, int W, int C,
                      int relu, void *dx, void *stream);
+/* The forward with its output written into the INTERIOR of a zero-bordered image yb [N, 2H+2, 2W+2, C] (x's dtype, 16-bit
+ * only): the operand layout of m3_conv3x3_fwd, so that the next stage's convolution reads what this stage wrote.  The border
+ * is the caller's: it must already be zero and is not touched.  The backward is m3_relu_up2x_bwd on the dense gradient. */
+int m3_relu_up2x_fwd_bordered(const void *x, int dtype, int64_t N, int H, int W, int C, int relu, void *yb, void *stream);
+
+/* -------------------------------------------------- decoder-head 3 x 3 convolutions ("custom later")
+ * nn.Conv2d(C, Cout, 3, stride 1, padding 1) of models/heads/vit_up_head.py:181-214 (conv_0..3) and of TamModule
+ * (models/models.py:11-134: layers0..3) as GEMMs on this library's own kernels (csrc/conv.hip), opt-in: 16-bit activations,
+ * C a multiple of 128, Cout a multiple of 8 (the input gradient: Cout a multiple of 128, C of 8).
+ * An activation that feeds a convolution is a zero-bordered channels-last image xb [N, H+2, W+2, C]; the window of output pixel
+ * m = (n, y, x) is three contiguous runs of 3 C elements, run dy starting at bordered pixel (n, y + dy, x), so the contraction
+ * index is ordered (dy, dx, c) and padding costs nothing.  pix_idx i32 [N H W]: bordered pixel index of (n, y, x), written by
+ * m3_conv3x3_index (once per shape).
+ *   m3_conv3x3_fwd    y [N H W, Cout] (dense channels-last, the activation dtype) = windows @ w^T (+ bias fp32 [Cout] or NULL);
+ *                     w [Cout, 9 C] = weight.permute(0, 2, 3, 1) in the activation dtype.  One launch of the 256 x 256 GEMM
+ *                     kernel with segmented A rows.
+ *   m3_conv3x3_dgrad  dx [N H W, C] from the zero-bordered dyb [N, H+2, W+2, Cout] and w_flip [C, 9 Cout] =
+ *                     weight.flip(2, 3).permute(1, 2, 3, 0): the same launch with the roles of C and Cout exchanged.
+ *   m3_conv3x3_wgrad  dw3 fp32 [3][Cout][3 C]: dw3[dy][co][dx C + c] = d weight[co][c][dy][dx], and db fp32 [Cout] (or NULL)
+ *                     from xb and the dense dy [N H W, Cout]: three m3_wgrad_tn problems (N = Cout, K = 3 C, one per kernel
+ *                     row) and one reduction; ws: m3_conv3x3_plan's wgrad_ws_elems floats.  Overwrites dw3 / db.
+ *   m3_pad_border_nhwc  xb = x [N, H, W, C] with a border of zeros (C a multiple of 8, 16-bit); bit-exact copy.
+ *   m3_conv3x3_plan   host code, no GPU work, reads no pointer: does the shape take this path (ok; reason = M3_CONV_OK or why
+ *                     not; dgrad_ok: the input gradient too), and with what: kernel / epilogue as m3_gemm_plan names them, the
+ *                     tile, row / column / K tile counts, K tiles per run (seg_tiles) and the byte jump between runs, the
+ *                     weight-gradient tile edge, its row parts and workspace.  A shape that is refused is no error. */
+#define M3_CONV_OK 0
+#define M3_CONV_REFUSE_DTYPE 1     /* not fp16 / bf16 */
+#define M3_CONV_REFUSE_CIN 2       /* input channels not a multiple of 128 */
+#define M3_CONV_REFUSE_COUT 3      /* output channels not a multiple of 8 */
+#define M3_CONV_REFUSE_REACH 4     /* bordered operand or weight panel past 4 GiB */
+typedef struct {
+  int32_t ok, reason, dgrad_ok;
+  int32_t kernel, epilogue;
+  int32_t tile_m, tile_n, m_tiles, n_tiles, k_tiles, seg_tiles;
+  int32_t wgrad_tile, wgrad_splits;
+  int64_t M, bordered_pixels, seg_jump_bytes, wgrad_ws_elems;
+} m3_conv3x3_plan_out;
+int m3_conv3x3_plan(int dtype, int64_t N, int H, int W, int C, int Cout, m3_conv3x3_plan_out *plan);
+int m3_conv3x3_index(int64_t N, int H, int W, int32_t *pix_idx, void *stream);
+int m3_pad_border_nhwc(const void *x, int dtype, int64_t N, int H, int W, int C, void *xb, void *stream);
+int m3_conv3x3_fwd(const void *xb, int dtype, int64_t N, int H, int W, int C, const void *w, int Cout, const float *bias,
+                   const int32_t *pix_idx, void *y, void *stream);
+int m3_conv3x3_dgrad(const void *dyb, int dtype, int64_t N, int H, int W, int C, const void *w_flip, int Cout,
+                     const int32_t *pix_idx, void *dx, void *stream);
+int m3_conv3x3_wgrad(const void *xb, const void *dy, int dtype, int64_t N, int H, int W, int C, int Cout,
+                     const int32_t *pix_idx, float *ws, int64_t ws_elems, float *dw3, float *db, void *stream);
 
 /* ------------------------------------------------------------- dense-prediction losses
  * The criterion between the decoder heads and the backward: the four losses utils/common_config.py:780-807 (get_loss) can

@@ -94,7 +94,7 @@ globals().update({py: STRUCTS["m3_" + c] for py, c in {         # the Python nam
     "WgradProblem": "wgrad_problem", "WgradMultiShape": "wgrad_multi_shape", "WgradMultiPlan": "wgrad_multi_plan_out",
     "WgradMultiArgs": "wgrad_multi_args", "AttentionPlan": "attention_plan_out", "CastDesc": "cast_desc",
     "OptimDesc": "optim_desc", "GateFwdArgs": "gate_fwd_args", "GateBwdArgs": "gate_bwd_args",
-    "LnParamGrads": "ln_param_grads", "AugmentDesc": "augment_desc"}.items()})
+    "LnParamGrads": "ln_param_grads", "AugmentDesc": "augment_desc", "Conv3x3Plan": "conv3x3_plan_out"}.items()})
 WGRAD_MULTI_MAX = CONSTANTS["M3_WGRAD_MULTI_MAX"]
 
 
@@ -105,6 +105,7 @@ def _names(prefix, but=" "):
 
 GEMM_KERNELS, GEMM_EPILOGUES = _names("M3_GEMM_", but="M3_GEMM_EPI_"), _names("M3_GEMM_EPI_")
 WGRAD_KERNELS, ATTN_FAMILIES = _names("M3_WGRAD_KERNEL_"), _names("M3_ATTN_")
+CONV_REASONS = _names("M3_CONV_")                               # m3_conv3x3_plan_out.reason: ok, refuse_dtype, ...
 
 
 def csrc_sha16() -> str:

@@ -45,7 +45,11 @@ enum { X_FULL = 0, X_PENULT = 1, X_LAST = 2 };
 
 #define X_LDSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off))
 
-template <typename T, int EPI>
+// SEG (the 3 x 3 convolutions of conv.hip): a row of A is not K contiguous elements but three runs of p.a_seg_tiles K tiles -
+// one per kernel row of a window in a zero-bordered channels-last image - whose starts lie one bordered image row apart.
+// Which run a K tile belongs to is wave-uniform: the A source of K tile kt moves by (kt / a_seg_tiles) * a_seg_jump_b bytes,
+// scalar arithmetic on the base.  The host guarantees nkt == 3 * a_seg_tiles with a_seg_tiles even.
+template <typename T, int EPI, bool SEG = false>
 __global__ __launch_bounds__(XT, 2) void gemm_nt_big_kernel(const GemmDev p) {
   typedef Mma<T> MM;
   typedef typename MM::frag frag;
@@ -147,6 +151,14 @@ __global__ __launch_bounds__(XT, 2) void gemm_nt_big_kernel(const GemmDev p) {
     for (int j = 0; j < 2; ++j)
       __builtin_amdgcn_global_load_lds((glb_void *)(b + src[j]), (lds_void *)(dma_dst + off + j * 1024), 16, 0, 0);
   };
+  auto issue_a = [&](const uint32_t (&src)[2], int kt, int off) {
+    if constexpr (SEG) {                             // (three runs: two compares instead of a division)
+      const int run = (kt >= p.a_seg_tiles ? 1 : 0) + (kt >= 2 * p.a_seg_tiles ? 1 : 0);
+      issue(baseA + (int64_t)run * p.a_seg_jump_b, src, kt, off);
+    } else {
+      issue(baseA, src, kt, off);
+    }
+  };
 
   // fragment read addresses (bytes from the start of a half-tile image): A row wr * 64 + 16 i + li, B row wc * 32 + 16 i + li
   const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_void *)smem;
@@ -166,11 +178,11 @@ __global__ __launch_bounds__(XT, 2) void gemm_nt_big_kernel(const GemmDev p) {
   frag fa[4][2], fb0[2][2], fb1[2][2];
 
   // ---- prologue: all of tile 0 and the first two half-tiles of tile 1
-  issue(baseA, srcA[0], 0, X_A0);
+  issue_a(srcA[0], 0, X_A0);
   issue(baseB, srcB[0], 0, X_B0);
   issue(baseB, srcB[1], 0, X_B1);
-  issue(baseA, srcA[1], 0, X_A1);
-  issue(baseA, srcA[0], 1, XSLOT + X_A0);
+  issue_a(srcA[1], 0, X_A1);
+  issue_a(srcA[0], 1, XSLOT + X_A0);
   issue(baseB, srcB[0], 1, XSLOT + X_B0);
   asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
   __builtin_amdgcn_s_barrier();                      // tile 0 has landed for every wave
@@ -206,12 +218,12 @@ __global__ __launch_bounds__(XT, 2) void gemm_nt_big_kernel(const GemmDev p) {
     // ---- phase 1: quadrant (m0, n1)
 #pragma unroll
     for (int i = 0; i < 2; ++i) { X_LDSR(fb1[i][0], b0, X_B1 + i * 2048); X_LDSR(fb1[i][1], b1, X_B1 + i * 2048); }
-    if constexpr (MODE != X_LAST) issue(baseA, srcA[1], kt + 1, O + X_A1);
+    if constexpr (MODE != X_LAST) issue_a(srcA[1], kt + 1, O + X_A1);
     X_MFMA_SEG(0, fb1, 1);
     // ---- phase 2: quadrant (m1, n1)
 #pragma unroll
     for (int i = 0; i < 4; ++i) { X_LDSR(fa[i][0], a0, X_A1 + i * 2048); X_LDSR(fa[i][1], a1, X_A1 + i * 2048); }
-    if constexpr (MODE == X_FULL) issue(baseA, srcA[0], kt + 2, S + X_A0);
+    if constexpr (MODE == X_FULL) issue_a(srcA[0], kt + 2, S + X_A0);
     X_MFMA_SEG(1, fb1, 1);
     // ---- phase 3: quadrant (m1, n0); the wait that makes tile kt + 1 readable from the next phase on
     if constexpr (MODE == X_FULL) {
@@ -367,6 +379,20 @@ int launch_gemm_big(const GemmDev &d, int dtype, int epi, hipStream_t s) {
   if (dtype == M3_F16) go(half_t());
   else go(bf16_t());
   return check_launch("m3_gemm_nt");
+}
+
+// The segmented-A instance (conv.hip fills d and has made the checks): PLAIN epilogue only
+int launch_gemm_big_seg(const GemmDev &d, int dtype, hipStream_t s, const char *who) {
+  static const bool attr_done = [] {
+    (void)hipFuncSetAttribute((const void *)gemm_nt_big_kernel<half_t, DMA_EPI_PLAIN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, XLDS);
+    (void)hipFuncSetAttribute((const void *)gemm_nt_big_kernel<bf16_t, DMA_EPI_PLAIN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, XLDS);
+    return true;
+  }();
+  (void)attr_done;
+  const dim3 grid((unsigned)((int64_t)d.m_tiles_max * d.n_tiles)), block(XT);
+  if (dtype == M3_F16) hipLaunchKernelGGL((gemm_nt_big_kernel<half_t, DMA_EPI_PLAIN, true>), grid, block, XLDS, s, d);
+  else hipLaunchKernelGGL((gemm_nt_big_kernel<bf16_t, DMA_EPI_PLAIN, true>), grid, block, XLDS, s, d);
+  return check_launch(who);
 }
 
 }  // namespace m3

@@ -33,6 +33,9 @@ struct GemmDev {
   int32_t m_band;                  // row tiles per band of the tile order (tile_of): 1 = row-tile major
   int32_t m_tiles_max;
   int32_t vec8;                                 // N and all leading dims multiples of 8: staged epilogue
+  // gemm_nt_big_kernel's segmented-A instance only (conv.hip; 0 elsewhere): a row of A is three runs of a_seg_tiles 128-byte
+  // K tiles, the start of a run a_seg_jump_b bytes behind the end of the run before it
+  int32_t a_seg_tiles; int64_t a_seg_jump_b;
 };
 
 // Grouped call: which (group, first row, end row) owns row tile mt, and how many workgroups are live.  G <= 64: ONE
@@ -141,6 +144,7 @@ int launch_gemm_staged(const GemmDev &d, int dtype, bool tall, hipStream_t s);  
 int launch_gemm_dma(const GemmDev &d, int dtype, int epi, hipStream_t s);             // 16-bit dtypes
 bool gemm_big_eligible(const GemmDev &d, int dtype_size_bytes, bool force);           // false: not a call the 256 x 256 kernel takes
 int launch_gemm_big(const GemmDev &d, int dtype, int epi, hipStream_t s);             // 16-bit dtypes
+int launch_gemm_big_seg(const GemmDev &d, int dtype, hipStream_t s, const char *who);  // segmented A rows, PLAIN epilogue (conv.hip)
 
 // Logical tile id -> (row tile, column tile).  Row-tile major (band 1): the n_tiles column tiles of a row tile are neighbours
 // (one XCD, one moment: the A rows come from HBM once).  When a column-tile's weight panel set does not fit the XCD's L2

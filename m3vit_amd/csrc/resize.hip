@@ -21,7 +21,9 @@ namespace m3 {
 constexpr int RZ_BYTES = 16;           // a thread's channels are one 16-byte vector of the INPUT dtype: Pack<T, RZ_BYTES / sizeof(T)>;
                                        // an fp32 output or gradient of a 16-bit input is the same count, two 16-byte accesses
 
-template <typename T, typename TO, bool RELU>
+// BORD: y is a zero-bordered image [N, 2H+2, 2W+2, C] whose interior is written (the operand layout of conv.hip; the border is
+// the caller's and is not touched)
+template <typename T, typename TO, bool RELU, bool BORD = false>
 __global__ __launch_bounds__(256) void relu_up2x_fwd_kernel(const T *__restrict__ x, int64_t total, int H, int W, int C,
                                                             TO *__restrict__ y) {
   constexpr int NV = RZ_BYTES / (int)sizeof(T);
@@ -57,8 +59,9 @@ __global__ __launch_bounds__(256) void relu_up2x_fwd_kernel(const T *__restrict_
       h[a][0][j] = 0.25f * z[a][0][j] + 0.75f * z[a][1][j];
       h[a][1][j] = 0.75f * z[a][1][j] + 0.25f * z[a][2][j];
     }
-  TO *out = y + ((n * 2 * H + 2 * iy) * (2 * (int64_t)W) + 2 * ix) * C + cv * NV;
-  const int64_t orow = 2 * (int64_t)W * C;
+  constexpr int PAD = BORD ? 1 : 0;
+  TO *out = y + ((n * (2 * H + 2 * PAD) + 2 * iy + PAD) * (2 * (int64_t)W + 2 * PAD) + 2 * ix + PAD) * C + cv * NV;
+  const int64_t orow = (2 * (int64_t)W + 2 * PAD) * C;
 #pragma unroll
   for (int b = 0; b < 2; ++b) {
     float o0[NV], o1[NV];
@@ -153,6 +156,26 @@ extern "C" int m3_relu_up2x_fwd(const void *x, int x_dtype, int64_t N, int H, in
     if (y_dtype == M3_F32) with_out(DtypeTag<float>{}); else with_out(tt);
   });
   return check_launch("m3_relu_up2x_fwd");
+}
+
+extern "C" int m3_relu_up2x_fwd_bordered(const void *x, int dtype, int64_t N, int H, int W, int C, int relu, void *yb, void *stream) {
+  M3_REQUIRE(x && yb, "m3_relu_up2x_fwd_bordered: null operand");
+  M3_REQUIRE(dtype == M3_F16 || dtype == M3_BF16, "m3_relu_up2x_fwd_bordered: 16-bit activations only");
+  M3_REQUIRE(rz_shape_ok(dtype, N, H, W, C) && N * (2 * H + 2) * (2 * (int64_t)W + 2) * C < ((int64_t)1 << 40),
+             "m3_relu_up2x_fwd_bordered: C must be a multiple of 8");
+  M3_REQUIRE(((uintptr_t)x % 16) == 0 && ((uintptr_t)yb % 16) == 0, "m3_relu_up2x_fwd_bordered: 16-byte aligned tensors");
+  if (N == 0) return M3_OK;
+  hipStream_t s = (hipStream_t)stream;
+  by_dtype(dtype, [&](auto tt) {
+    typedef typename decltype(tt)::type T;
+    if constexpr (sizeof(T) == 2) {
+      const int64_t total = N * H * (int64_t)W * (C / (RZ_BYTES / (int)sizeof(T)));
+      const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+      if (relu) hipLaunchKernelGGL((relu_up2x_fwd_kernel<T, T, true, true>), grid, block, 0, s, (const T *)x, total, H, W, C, (T *)yb);
+      else hipLaunchKernelGGL((relu_up2x_fwd_kernel<T, T, false, true>), grid, block, 0, s, (const T *)x, total, H, W, C, (T *)yb);
+    }
+  });
+  return check_launch("m3_relu_up2x_fwd_bordered");
 }
 
 extern "C" int m3_relu_up2x_bwd(const void *dy, int dy_dtype, const void *x, int x_dtype, int64_t N, int H, int W, int C,

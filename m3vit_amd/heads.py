@@ -12,11 +12,15 @@ Also mirrored, as plain torch modules behind the path (convolutions = MIOpen): t
 (`output_level_0..2`, vit_up_head.py:128-131,184-214), their three TAM feature taps (:190-206) and `TamModule`
 (models/models.py:11-134: a sigmoid gate B from the stacked task features, a 2x down / 2x up modulation M, one
 3x3 + 1x1 head per task on cat_t(feature_t * (1 + M))), wired into `MultiTaskModel` as `tam_level0/1/2` (:246-279).
+Opt-in, `conv="gemm"` on the head and on `TamModule`: their 3 x 3, stride-1 convolutions become `m3vit_amd.conv.Conv3x3`, which
+under 16-bit autocast runs forward, input gradient and weight gradient on the project's GEMM kernels (csrc/conv.hip); the
+default `conv="miopen"` is the behaviour described above, bit for bit.
 The sem regulariser is out of scope."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .conv import Conv3x3, bordered_buffer, relu_up2x_bordered
 from .functional import LayerNormFn
 
 
@@ -49,15 +53,40 @@ def _fusable(x, align_corners):
             and x.is_contiguous(memory_format=torch.channels_last) and x.shape[1] % (4 if x.dtype == torch.float32 else 8) == 0)
 
 
+def _conv_cls(conv):
+    """the class of the 3 x 3, stride-1 convolutions for a module's `conv` option: "miopen" (default) nn.Conv2d, "gemm" Conv3x3
+    (m3vit_amd/conv.py: the project's GEMM kernels where they apply, same parameters and state_dict keys)"""
+    if conv not in ("miopen", "gemm"):
+        raise ValueError(f'conv must be "miopen" or "gemm", got {conv!r}')
+    return Conv3x3 if conv == "gemm" else nn.Conv2d
+
+
+def _gemm_operand(x):
+    """conv="gemm" under 16-bit autocast on the GPU: x as the 16-bit channels-last tensor Conv3x3 takes - the values autocast's
+    own cast would hand MIOpen, in the other memory format.  Anything else passes through (and Conv3x3 then runs MIOpen)."""
+    if not (x.is_cuda and torch.is_autocast_enabled()) or bordered_buffer(x) is not None:
+        return x
+    dt = torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
+    if dt not in (torch.float16, torch.bfloat16):
+        return x
+    return x.to(dt).contiguous(memory_format=torch.channels_last)
+
+
 class VisionTransformerUpHead(nn.Module):
     def __init__(self, img_size=(480, 640), patch_size=16, embed_dim=384, num_classes=40, num_conv=4,
                  num_upsampe_layer=4, conv3x3_conv1x1=True, align_corners=False, sync_bn=False,
-                 act_dtype=torch.float32, channels=256, multi_level=False, tam=False, amp=False, fused_resize=True):
+                 act_dtype=torch.float32, channels=256, multi_level=False, tam=False, amp=False, fused_resize=True,
+                 conv="miopen"):
         """amp: run the conv / BN / resize stages under fp16 autocast on the GPU, as the reference does under its AMP step
         (pretrain/engine/train_one_epoch.py:35-61): at 480 x 640 (8 images, 40 classes) forward + backward 33.4 -> 13.9 ms,
         MIOpen's fp16 3x3 convolutions running at 406-475 TFLOP/s (tools/head_bench.py)."""
         super().__init__()
         self.amp = bool(amp)
+        # conv: "miopen" (default) - the 3 x 3 convolutions are nn.Conv2d; "gemm" - they are Conv3x3 (m3vit_amd/conv.py), which
+        # under 16-bit autocast run on the GEMM kernels, each stage's ReLU + x2 writing the next one's zero-bordered operand.
+        # The 1 x 1 classifiers stay MIOpen's; module names and state_dict keys are the same either way
+        Conv = _conv_cls(conv)
+        self.conv = conv
         # fused_resize: ReLU + bilinear x2 of a stage as one hand-written kernel each way (ReluUp2xFn) whenever the stage's
         # tensor is channels-last on the GPU; forward + backward of the head at 480 x 640 under autocast: 13.7 -> see
         # tools/head_bench.py.  False: torch's relu + interpolate (what rounds 1-3 ran)
@@ -74,13 +103,13 @@ class VisionTransformerUpHead(nn.Module):
         self.norm = nn.LayerNorm(embed_dim, eps=1e-6)
         bn = nn.SyncBatchNorm if sync_bn else nn.BatchNorm2d
         if num_conv == 2:
-            self.conv_0 = nn.Conv2d(embed_dim, channels, 3, 1, 1) if conv3x3_conv1x1 else nn.Conv2d(embed_dim, channels, 1, 1)
+            self.conv_0 = Conv(embed_dim, channels, 3, 1, 1) if conv3x3_conv1x1 else nn.Conv2d(embed_dim, channels, 1, 1)
             self.conv_1 = nn.Conv2d(channels, num_classes, 1, 1)
             self.syncbn_fc_0 = bn(channels)
         else:
-            self.conv_0 = nn.Conv2d(embed_dim, channels, 3, 1, 1)
+            self.conv_0 = Conv(embed_dim, channels, 3, 1, 1)
             for i in (1, 2, 3):
-                setattr(self, f"conv_{i}", nn.Conv2d(channels, channels, 3, 1, 1))
+                setattr(self, f"conv_{i}", Conv(channels, channels, 3, 1, 1))
             self.conv_4 = nn.Conv2d(channels, num_classes, 1, 1)
             for i in range(4):
                 setattr(self, f"syncbn_fc_{i}", bn(channels))
@@ -107,6 +136,9 @@ class VisionTransformerUpHead(nn.Module):
         return self._stages(x)
 
     def _stages(self, x):
+        gemm = self.conv == "gemm"
+        if gemm:
+            x = _gemm_operand(x)
         if self.num_conv == 2:
             x = F.relu(self.syncbn_fc_0(self.conv_0(x)))
             if self.num_upsampe_layer == 2:
@@ -117,13 +149,18 @@ class VisionTransformerUpHead(nn.Module):
         for i in range(4):
             x = getattr(self, f"syncbn_fc_{i}")(getattr(self, f"conv_{i}")(x))
             if self.fused_resize and i < 3 and not (want_taps and i >= 1) and _fusable(x, self.align_corners):
-                x = ReluUp2xFn.apply(x, True, False)                     # relu + resize in one pass, dtype kept
+                if gemm and not self.multi_level and x.dtype != torch.float32:
+                    x = relu_up2x_bordered(x)                            # the same pass, written as the next conv's operand
+                else:
+                    x = ReluUp2xFn.apply(x, True, False)                 # relu + resize in one pass, dtype kept
             else:
                 x = F.relu(x)
                 if i >= 1:
                     taps.append(x)                                       # tam_feature0..2: after conv_1..3 (:190-206)
                 if i < 3:
                     x = self._up(x, 2)
+                    if gemm:
+                        x = _gemm_operand(x)
             if i < 3 and self.multi_level:
                 out[f"level{i + 1}"] = getattr(self, f"output_level_{i}")(x)     # :184-200
         x = self.conv_4(x)
@@ -141,20 +178,24 @@ class TamModule(nn.Module):
     norm: the layer build_norm_layer(norm_cfg) would give (BatchNorm2d / SyncBatchNorm).  The reference's activation
     checkpointing around the blocks changes memory only."""
 
-    def __init__(self, tasks, input_channels, num_output, norm=nn.BatchNorm2d):
+    def __init__(self, tasks, input_channels, num_output, norm=nn.BatchNorm2d, conv="miopen"):
+        """conv: as in VisionTransformerUpHead - "gemm" makes the 3 x 3, stride-1 convolutions (layers0..3) Conv3x3; the strided,
+        transposed and 1 x 1 ones stay MIOpen's"""
         super().__init__()
+        Conv = _conv_cls(conv)
+        self.conv = conv
         self.tasks = list(tasks)
         if not 2 <= len(self.tasks) <= 5:
             raise ValueError("TamModule is defined for 2..5 tasks (models/models.py:87-95)")
         nt, c = len(self.tasks), input_channels
-        self.layers0 = nn.Sequential(nn.Conv2d(nt * c, c, 3, 1, 1), norm(c))
-        self.layers1 = nn.Sequential(nn.Conv2d(c, c, 3, 1, 1), norm(c))
-        self.layers2 = nn.Sequential(nn.Conv2d(nt * c, c, 3, 1, 1), norm(c))
+        self.layers0 = nn.Sequential(Conv(nt * c, c, 3, 1, 1), norm(c))
+        self.layers1 = nn.Sequential(Conv(c, c, 3, 1, 1), norm(c))
+        self.layers2 = nn.Sequential(Conv(nt * c, c, 3, 1, 1), norm(c))
         self.encoder0 = nn.Sequential(nn.Conv2d(c, c, 3, 2, 1), norm(c))
         self.encoder1 = nn.Sequential(nn.Conv2d(c, c, 3, 2, 1), norm(c))
         self.decoder0 = nn.Sequential(nn.ConvTranspose2d(c, c, 3, 2, 1, output_padding=1), norm(c))
         self.decoder1 = nn.Sequential(nn.ConvTranspose2d(c, c, 3, 2, 1, output_padding=1), norm(c))
-        self.layers3 = nn.ModuleDict({t: nn.Sequential(nn.Conv2d(nt * c, 256, 3, 1, 1), norm(256)) for t in self.tasks})
+        self.layers3 = nn.ModuleDict({t: nn.Sequential(Conv(nt * c, 256, 3, 1, 1), norm(256)) for t in self.tasks})
         self.layers4 = nn.ModuleDict({t: nn.Sequential(nn.Conv2d(256, num_output[t], 1, 1)) for t in self.tasks})
 
     @staticmethod
@@ -167,12 +208,14 @@ class TamModule(nn.Module):
         feats = [deepfeature[t] for t in self.tasks]
         batch, c, H, W = feats[0].shape
         stacked = torch.stack(feats, dim=1).reshape(batch, len(feats) * c, H, W)
-        B = torch.sigmoid(self.layers1(F.relu(self.layers0(stacked))))                       # _block0
+        op = _gemm_operand if self.conv == "gemm" else (lambda t: t)
+        B = torch.sigmoid(self.layers1(op(F.relu(self.layers0(op(stacked))))))               # _block0
         Fb = torch.cat([f * w for f, w in zip(feats, self.gate_weights(len(feats), B))], dim=1)
-        Fb = F.relu(self.layers2(Fb))                                                        # _block2
+        Fb = F.relu(self.layers2(op(Fb)))                                                    # _block2
         Fb = F.relu(self.encoder1(F.relu(self.encoder0(Fb))))                                # _encoder_block
         M = torch.sigmoid(self.decoder1(F.relu(self.decoder0(Fb))))                          # _decoder_block
         Ftam = torch.cat([f * (1 + M) for f in feats], dim=1)
+        Ftam = op(Ftam)
         return {t: self.layers4[t](F.relu(self.layers3[t](Ftam))) for t in self.tasks}
 
 

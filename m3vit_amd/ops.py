@@ -1564,6 +1564,120 @@ def relu_up2x_bwd(dy, x, relu=True):
     return dx
 
 
+# ---- 3 x 3 convolutions of the decoder heads on the GEMM kernels (csrc/conv.hip; include/m3vit_hip.h: m3_conv3x3_*).
+# A bordered activation is a contiguous 16-bit tensor [N, H+2, W+2, C] whose border is zero.
+
+def conv3x3_plan(dtype, N, H, W, C, Cout) -> _lib.Conv3x3Plan:
+    """m3_conv3x3_plan: .ok / .reason (names: _lib.CONV_REASONS) / .dgrad_ok, the kernel, tile counts and the weight-gradient
+    workspace of a [N, C, H, W] -> Cout convolution on the GEMM path.  Host code: launches nothing, needs no GPU."""
+    p = _lib.Conv3x3Plan()
+    check(lib().m3_conv3x3_plan(dt_code(dtype), N, H, W, C, Cout, byref(p)), "m3_conv3x3_plan")
+    return p
+
+
+_CONV_INDEX = {}
+
+
+def conv3x3_index(N, H, W, device):
+    """the int32 table pixel (n, y, x) -> bordered pixel index, built on the device once per (shape, device)"""
+    key = (N, H, W, torch.device(device))
+    idx = _CONV_INDEX.get(key)
+    if idx is None:
+        idx = torch.empty(max(N * H * W, 1), dtype=torch.int32, device=device)
+        check(lib().m3_conv3x3_index(N, H, W, _p(idx), _stream()), "m3_conv3x3_index")
+        if not torch.cuda.is_current_stream_capturing():
+            _CONV_INDEX[key] = idx
+    return idx
+
+
+def _bordered(t, name):
+    """(N, H, W, C) of a bordered activation [N, H+2, W+2, C]"""
+    N, HB, WB, C = _dims(t, 4, name)
+    _req(t, name=name)
+    if t.dtype not in (torch.float16, torch.bfloat16):
+        raise _lib.M3Error(f"{name} must be float16 or bfloat16, got {t.dtype}")
+    if HB < 3 or WB < 3:
+        raise _lib.M3Error(f"{name} must be a bordered image [N, H+2, W+2, C], got shape {tuple(t.shape)}")
+    return N, HB - 2, WB - 2, C
+
+
+def pad_border(x, out=None):
+    """channels-last [N, C, H, W] (16-bit) -> bordered [N, H+2, W+2, C], the border written as zeros (m3_pad_border_nhwc)"""
+    _nhwc(x, "x")
+    N, C, H, W = x.shape
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise _lib.M3Error(f"x must be float16 or bfloat16, got {x.dtype}")
+    xb = torch.empty((N, H + 2, W + 2, C), dtype=x.dtype, device=x.device) if out is None else out
+    _req(xb, x.dtype, "out", numel=N * (H + 2) * (W + 2) * C)
+    check(lib().m3_pad_border_nhwc(_p(x), dt_code(x.dtype), N, H, W, C, _p(xb), _stream()), "m3_pad_border_nhwc")
+    return xb
+
+
+def relu_up2x_fwd_bordered(x, relu=True, out=None):
+    """bilinear x2 of relu(x), channels-last [N, C, H, W] (16-bit) -> bordered [N, 2H+2, 2W+2, C] (m3_relu_up2x_fwd_bordered).
+    out: a bordered buffer whose border is already zero; without it one is allocated and its border zeroed here."""
+    _nhwc(x, "x")
+    N, C, H, W = x.shape
+    if x.dtype not in (torch.float16, torch.bfloat16):
+        raise _lib.M3Error(f"x must be float16 or bfloat16, got {x.dtype}")
+    if out is None:
+        out = torch.empty((N, 2 * H + 2, 2 * W + 2, C), dtype=x.dtype, device=x.device)
+        out[:, 0].zero_(); out[:, -1].zero_(); out[:, :, 0].zero_(); out[:, :, -1].zero_()
+    _req(out, x.dtype, "out", numel=N * (2 * H + 2) * (2 * W + 2) * C)
+    check(lib().m3_relu_up2x_fwd_bordered(_p(x), dt_code(x.dtype), N, H, W, C, 1 if relu else 0, _p(out), _stream()),
+          "m3_relu_up2x_fwd_bordered")
+    return out
+
+
+def conv3x3_fwd(xb, w, bias=None, out=None):
+    """y [N H W, Cout] = conv3x3(bordered xb [N, H+2, W+2, C], w [Cout, 9 C] in (dy, dx, c) order) (+ bias fp32) - m3_conv3x3_fwd"""
+    N, H, W, C = _bordered(xb, "xb")
+    Cout = _dims(w, 2, "w")[0]
+    _req(w, xb.dtype, "w", numel=Cout * 9 * C)
+    if bias is not None:
+        _req(bias, torch.float32, "bias", numel=Cout)
+    y = torch.empty((N * H * W, Cout), dtype=xb.dtype, device=xb.device) if out is None else out
+    _req(y, xb.dtype, "out", numel=N * H * W * Cout)
+    check(lib().m3_conv3x3_fwd(_p(xb), dt_code(xb.dtype), N, H, W, C, _p(w), Cout, _p(bias),
+                               _p(conv3x3_index(N, H, W, xb.device)), _p(y), _stream()), "m3_conv3x3_fwd")
+    return y
+
+
+def conv3x3_dgrad(dyb, w_flip, out=None):
+    """dx [N H W, C] from the bordered dyb [N, H+2, W+2, Cout] and w_flip [C, 9 Cout] = weight.flip(2, 3).permute(1, 2, 3, 0)
+    (m3_conv3x3_dgrad)"""
+    N, H, W, Cout = _bordered(dyb, "dyb")
+    C = _dims(w_flip, 2, "w_flip")[0]
+    _req(w_flip, dyb.dtype, "w_flip", numel=C * 9 * Cout)
+    dx = torch.empty((N * H * W, C), dtype=dyb.dtype, device=dyb.device) if out is None else out
+    _req(dx, dyb.dtype, "out", numel=N * H * W * C)
+    check(lib().m3_conv3x3_dgrad(_p(dyb), dt_code(dyb.dtype), N, H, W, C, _p(w_flip), Cout,
+                                 _p(conv3x3_index(N, H, W, dyb.device)), _p(dx), _stream()), "m3_conv3x3_dgrad")
+    return dx
+
+
+def conv3x3_wgrad(xb, dy, dw3=None, db=None, ws=None):
+    """dw3 fp32 [3, Cout, 3 C] (dw3[dy, co, dx C + c] = d weight[co, c, dy, dx]) and, when db fp32 [Cout] is given, the bias
+    gradient, from the bordered xb [N, H+2, W+2, C] and the dense dy [N H W, Cout] (m3_conv3x3_wgrad).  Both are overwritten."""
+    N, H, W, C = _bordered(xb, "xb")
+    Cout = _dims(dy, 2, "dy")[1]
+    _req(dy, xb.dtype, "dy", numel=N * H * W * Cout)
+    p = conv3x3_plan(xb.dtype, N, H, W, C, Cout)
+    if not p.ok:
+        raise _lib.M3Error(f"conv3x3_wgrad: the shape does not take the GEMM path ({_lib.CONV_REASONS[p.reason]})")
+    if dw3 is None:
+        dw3 = torch.empty((3, Cout, 3 * C), dtype=torch.float32, device=xb.device)
+    _req(dw3, torch.float32, "dw3", numel=3 * Cout * 3 * C)
+    if db is not None:
+        _req(db, torch.float32, "db", numel=Cout)
+    if ws is None:
+        ws = torch.empty(max(p.wgrad_ws_elems, 4), dtype=torch.float32, device=xb.device)
+    _req(ws, torch.float32, "ws", min_numel=p.wgrad_ws_elems)
+    check(lib().m3_conv3x3_wgrad(_p(xb), _p(dy), dt_code(xb.dtype), N, H, W, C, Cout, _p(conv3x3_index(N, H, W, xb.device)),
+                                 _p(ws), ws.numel(), _p(dw3), _p(db), _stream()), "m3_conv3x3_wgrad")
+    return dw3
+
+
 def im2row(img, P, rows):
     B, Cin, H, W = _dims(img, 4, "img")
     if P < 1 or H % P or W % P:
