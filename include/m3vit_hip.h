@@ -44,6 +44,19 @@ int m3_version(void);
 const char *m3_last_error(void);
 /* fills name[0..len) with the gcnArchName of the current device; returns CU count or <0 */
 int m3_device_query(char *name, int len);
+/* Tuning knob, no reference counterpart: cache policy by tensor lifetime.  One bit per kernel family; a family whose bit is
+ * set launches the instance of its kernel whose loads of a tensor that is dead for the rest of the pass, and whose stores
+ * of a tensor that is next read a whole backward later, carry the non-temporal hint.  Tensors that the next kernels read
+ * (hand-offs) are never hinted.  The hint moves no arithmetic: every result is bit-identical under every mask.
+ *   M3_HINT_GEMM_PRE   m3_gemm_nt, GELU kind of the LDS-DMA kernel: the store of pre_out
+ *   M3_HINT_GEMM_GPRE  m3_gemm_nt, GPRE kind of the LDS-DMA kernel: the load of gelu_grad_pre
+ * mask: an OR of the bits, or -1 = re-read M3_CACHE_HINTS (unset: M3_HINT_DEFAULT, the families that measured faster in the
+ * training step).  Takes effect with the next launch; a captured graph keeps the instances it was captured with. */
+#define M3_HINT_GEMM_PRE 1
+#define M3_HINT_GEMM_GPRE 2
+#define M3_HINT_ALL 3
+#define M3_HINT_DEFAULT 3
+int m3_set_cache_hints(int mask);
 
 /* ---------------------------------------------------------------- gate (a1-a3)
  * NoisyGate_VMoE.forward, models/moe/ckpt/noisy_gate_vmoe.py:91-93,168,197-207:

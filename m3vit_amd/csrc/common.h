@@ -178,6 +178,29 @@ template <> struct Vec8<bf16_t> {
   }
 };
 
+// ------------------------------------------------------------------ cache policy by tensor lifetime
+// A load whose tensor is dead for the rest of the pass, or a store whose next reader is a whole backward away, carries the
+// non-temporal hint: the line is not kept for a reader that will not come, and the hand-off tensors the neighbouring kernels
+// pass on stay in the cache.  NT is a template constant of the kernel: the hinted instance is the plain one but for the
+// modifier.  Which families use it: m3_set_cache_hints (include/m3vit_hip.h).
+int cache_hints();                                   // the current mask (lib.hip)
+template <bool NT, typename V> __device__ __forceinline__ V ld_nt(const V *p) {
+  if constexpr (NT) return __builtin_nontemporal_load(p);
+  else return *p;
+}
+template <bool NT, typename V> __device__ __forceinline__ void st_nt(V *p, V v) {
+  if constexpr (NT) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+// 8 consecutive elements of a 16-bit T as one 16-byte register value (what Vec8<T>::store writes)
+template <typename T> __device__ __forceinline__ u32x4 pack8(f32x4 a, f32x4 b) {
+  typedef T t8 __attribute__((ext_vector_type(8)));
+  t8 h;
+  h[0] = (T)a[0]; h[1] = (T)a[1]; h[2] = (T)a[2]; h[3] = (T)a[3];
+  h[4] = (T)b[0]; h[5] = (T)b[1]; h[6] = (T)b[2]; h[7] = (T)b[3];
+  return __builtin_bit_cast(u32x4, h);
+}
+
 // V consecutive elements of T <-> V floats, for kernels that keep their values as float arrays: V = 1 a scalar access,
 // V = 4 and 8 the accesses of Vec4 / Vec8
 template <typename T, int V> struct Pack;

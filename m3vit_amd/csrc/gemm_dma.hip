@@ -23,8 +23,11 @@ constexpr int DMA_RB = 128;                // bytes of a row slice = one cache l
 constexpr int DMA_LDS = 2 * BM * DMA_RB;   // A + B image: 32 KiB
 constexpr int DMA_LDS_ALL = DMA_LDS + BM * 4;   // + the tile's 128 per-row epilogue factors (row_scale)
 
-// EPI: the epilogue's kind (gemm_dev.h)
-template <typename T, int EPI>
+// EPI: the epilogue's kind (gemm_dev.h).  HINT: the kind's one access to a tensor that nobody reads soon is non-temporal
+// (common.h: cache policy by lifetime) - GELU: the store of pre_out, next read by the backward; GPRE: the load of gpre, its
+// last use.  Everything else about the instance is the plain one.  (Operand loads stay plain: the column tiles of a row tile
+// re-read A through L2, and with the hint on the LDS-DMA loads of A the step measured 0.6 ms slower.)
+template <typename T, int EPI, bool HINT>
 __global__ __launch_bounds__(GEMM_THREADS, 4) void gemm_nt_dma_kernel(const GemmDev p) {
   typedef Mma<T> MM;
   typedef typename MM::frag frag;
@@ -171,7 +174,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void gemm_nt_dma_kernel(const Gemm
     // this wave's accumulators are on their way out - all four at once did not fit the 128-register budget)
     constexpr int NPRE = EPI == DMA_EPI_RES ? 2 : 4;
     auto fetch_epi = [&](int ps) {
-      if constexpr (EPI == DMA_EPI_GPRE) gq[ps] = *(const u32x4 *)((const T *)p.gpre + (int64_t)crow4[ps] * p.ld_gpre + n);
+      if constexpr (EPI == DMA_EPI_GPRE) gq[ps] = ld_nt<HINT>((const u32x4 *)((const T *)p.gpre + (int64_t)crow4[ps] * p.ld_gpre + n));
       if constexpr (EPI == DMA_EPI_RES) {
         rq[ps][0] = *(const f32x4 *)(p.residual + (int64_t)crow4[ps] * p.ld_res + n);
         rq[ps][1] = *(const f32x4 *)(p.residual + (int64_t)crow4[ps] * p.ld_res + n + 4);
@@ -214,7 +217,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void gemm_nt_dma_kernel(const Gemm
           f32x4 v1 = *(const f32x4 *)(smem + lrow * 512 + (((2 * cg + 1) ^ sw) << 4));
           v0 += b0; v1 += b1;
           if constexpr (EPI == DMA_EPI_GELU) {
-            Vec8<T>::store((T *)p.pre_out + crow * p.ld_pre + n, v0, v1);
+            if constexpr (HINT) st_nt<true>((u32x4 *)((T *)p.pre_out + crow * p.ld_pre + n), pack8<T>(v0, v1));
+            else Vec8<T>::store((T *)p.pre_out + crow * p.ld_pre + n, v0, v1);
 #pragma unroll
             for (int j = 0; j < 4; ++j) { v0[j] = gelu_f(v0[j]); v1[j] = gelu_f(v1[j]); }
           }
@@ -254,9 +258,16 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void gemm_nt_dma_kernel(const Gemm
 
 int launch_gemm_dma(const GemmDev &d, int dtype, int epi, hipStream_t s) {
   const dim3 grid((unsigned)((int64_t)d.m_tiles_max * d.n_tiles)), block(GEMM_THREADS);
+  const int hints = cache_hints();
   auto go = [&](auto t) {
     with_epi(epi, [&](auto e) {
-      hipLaunchKernelGGL((gemm_nt_dma_kernel<decltype(t), decltype(e)::value>), grid, block, DMA_LDS_ALL, s, d);
+      constexpr int EPI = decltype(e)::value;
+      constexpr int BIT = EPI == DMA_EPI_GELU ? M3_HINT_GEMM_PRE : EPI == DMA_EPI_GPRE ? M3_HINT_GEMM_GPRE : 0;   // 0: no hinted instance
+      if (BIT && (hints & BIT)) {
+        hipLaunchKernelGGL((gemm_nt_dma_kernel<decltype(t), EPI, BIT != 0>), grid, block, DMA_LDS_ALL, s, d);
+      } else {
+        hipLaunchKernelGGL((gemm_nt_dma_kernel<decltype(t), EPI, false>), grid, block, DMA_LDS_ALL, s, d);
+      }
     });
   };
   if (dtype == M3_F16) go(half_t());

@@ -1,5 +1,6 @@
 // Host-side plumbing of libm3vit_hip.so: error text, version, device query.
 #include <stdarg.h>
+#include <stdlib.h>
 
 #include "common.h"
 
@@ -23,7 +24,23 @@ int check_launch(const char *what) {
   return M3_OK;
 }
 
+// m3_set_cache_hints' mask; < 0: the next launch reads M3_CACHE_HINTS (unset: the families that measured faster)
+static int g_cache_hints = -1;
+int cache_hints() {
+  if (g_cache_hints < 0) {
+    const char *e = getenv("M3_CACHE_HINTS");
+    g_cache_hints = (e ? atoi(e) : M3_HINT_DEFAULT) & M3_HINT_ALL;
+  }
+  return g_cache_hints;
+}
+
 }  // namespace m3
+
+extern "C" int m3_set_cache_hints(int mask) {
+  M3_REQUIRE(mask >= -1 && mask <= M3_HINT_ALL, "m3_set_cache_hints: mask %d out of range", mask);
+  m3::g_cache_hints = mask;
+  return M3_OK;
+}
 
 extern "C" int m3_version(void) { return 100; }   // 0.1.0
 

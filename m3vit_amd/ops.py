@@ -405,6 +405,12 @@ def gemm_set_big(mode: int):
     check(lib().m3_gemm_set_big(int(mode)), "m3_gemm_set_big")
 
 
+def set_cache_hints(mask: int):
+    """which kernel families run their non-temporal instances (include/m3vit_hip.h: m3_set_cache_hints): an OR of the
+    M3_HINT_* bits, -1 re-reads M3_CACHE_HINTS (unset: M3_HINT_DEFAULT).  Results are bit-identical under every mask."""
+    check(lib().m3_set_cache_hints(int(mask)), "m3_set_cache_hints")
+
+
 _WGRAD_DIRECT = os.environ.get("M3_WGRAD_DIRECT", "1") != "0"      # one part per group: the kernel accumulates into dW itself (no slabs)
 
 
