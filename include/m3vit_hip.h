@@ -290,7 +290,9 @@ int m3_gemm_plan(const m3_gemm_args *args, m3_gemm_plan_out *plan);
  *   nn.Linear weight grads.  dC [*, N], A [*, K] in the act dtype; dW fp32 [G][N][K].
  * Deterministic split over rows: `splits` partial slabs in ws (fp32
  * [splits][G][N][K]) then m3_wgrad_reduce sums them in order (beta = 1 accumulates
- * into dW, as the joint multi-task backward does: train/train_utils.py:449-457). */
+ * into dW, as the joint multi-task backward does: train/train_utils.py:449-457).
+ * M < 2^31 rows and row strides (lddc, lda times the element size) below 4 GiB: the kernels form a row's byte offset as one
+ * 32 x 32 -> 64-bit product; a call outside either is refused (m3_wgrad_multi alike). */
 /* A slab reduction that has not been launched yet (the arguments of m3_wgrad_reduce, or with chunk_rows > 0 of
  * m3_wgrad_reduce_grouped): the next m3_wgrad_tn call of the stream can carry it out in front of its own work
  * (m3_wgrad_args.prev), which saves one launch per weight-gradient GEMM. */
@@ -408,6 +410,13 @@ typedef struct {
   int64_t ws_elems;                /* fp32 elements: units * N * (K + bias); 0 in direct mode */
 } m3_wgrad_plan_out;
 int m3_wgrad_plan(const m3_wgrad_shape *shape, m3_wgrad_plan_out *plan);
+/* The unit map of balanced mode as a host query (no GPU work; group_offsets is HOST memory here, [G + 1], 1 <= G <= 64;
+ * chunk_rows a multiple of 64): group g gets n_g = ceil(rows_g / chunk_rows) consecutive units, unit j of them covers rows
+ * [j * share_g, min((j + 1) * share_g, rows_g)) of the group with share_g = ceil(rows_g / n_g) rounded up to 64 (<= chunk_rows:
+ * no unit is empty or longer than chunk_rows, an empty group has none).  Writes the group of `unit` and its rows as indices
+ * into the call's M rows; group = -1 and no rows for a unit past the last one (a slab slot without work).  The same two
+ * functions compute the map in the kernels and in m3_wgrad_reduce_grouped. */
+int m3_wgrad_unit_of(const int32_t *group_offsets, int G, int chunk_rows, int unit, int *group, int *row_begin, int *row_end);
 /* Tuning knob, no reference counterpart: which weight-gradient launches take the LDS-DMA kernel (wgrad_dma_kernel,
  * csrc/wgrad_dma.hip: four workgroups per CU, operands global -> LDS directly; fp16 / bf16 / fp32, power-of-two gather divisors, a
  * per-row factor with fp16 / fp32 only).  0 = none (the register-staged kernel everywhere), 2 = every launch the kernel can

@@ -294,6 +294,30 @@ extern "C" int m3_wgrad_plan(const m3_wgrad_shape *s, m3_wgrad_plan_out *p) {
   return M3_OK;
 }
 
+// The unit map of a balanced grouped call on the host: the groups walked in order with the two rules the kernels use
+// (wgrad_dev.h: wgrad_units_of_group, wgrad_unit_rows)
+extern "C" int m3_wgrad_unit_of(const int32_t *group_offsets, int G, int chunk_rows, int unit, int *group, int *row_begin,
+                                int *row_end) {
+  M3_REQUIRE(group_offsets && group && row_begin && row_end, "m3_wgrad_unit_of: null argument");
+  M3_REQUIRE(G >= 1 && G <= 64 && chunk_rows >= WG_ROWS && chunk_rows % WG_ROWS == 0 && unit >= 0,
+             "m3_wgrad_unit_of: needs 1 <= G <= 64, chunk_rows a multiple of %d and unit >= 0", WG_ROWS);
+  *group = -1; *row_begin = *row_end = 0;
+  int first = 0;
+  for (int g = 0; g < G; ++g) {
+    const int rows = group_offsets[g + 1] - group_offsets[g];
+    M3_REQUIRE(rows >= 0, "m3_wgrad_unit_of: group_offsets decrease at group %d", g);
+    const int n = wgrad_units_of_group(rows, chunk_rows);
+    if (unit < first + n) {
+      int b, e;
+      wgrad_unit_rows(rows, n, unit - first, b, e);
+      *group = g; *row_begin = group_offsets[g] + b; *row_end = group_offsets[g] + e;
+      return M3_OK;
+    }
+    first += n;
+  }
+  return M3_OK;                                      // a surplus unit: the launch's workgroups of this id have no work
+}
+
 // ------------------------------------------------------------------ slab reductions
 // 16-byte columns per block of the dense slab reduction: four threads per column from 32 slabs on
 static inline int m3_wgrad_reduce_cols(int splits) { return splits >= 32 ? 64 : 256; }
@@ -447,6 +471,8 @@ static int wgrad_prepare(const m3_wgrad_args *a, const char *who, WgradDev &d, W
   M3_REQUIRE(a->M < ((int64_t)1 << 31), "%s: M exceeds the 32-bit row indices", who);
   M3_REQUIRE((a->N * es) % 16 == 0 && (a->K * es) % 16 == 0, "%s: N*elem and K*elem must be multiples of 16 bytes", who);
   M3_REQUIRE((a->lddc * es) % 16 == 0 && (a->lda * es) % 16 == 0, "%s: rows must be 16-byte aligned", who);
+  M3_REQUIRE(a->lddc >= 0 && a->lda >= 0 && a->lddc * es < ((int64_t)1 << 32) && a->lda * es < ((int64_t)1 << 32),
+             "%s: a row stride of 4 GiB or more (the kernels form row offsets from 32-bit rows and strides)", who);
   M3_REQUIRE(((uintptr_t)a->dC % 16) == 0 && ((uintptr_t)a->A % 16) == 0 && ((uintptr_t)a->ws % 16) == 0, "%s: alignment", who);
   M3_REQUIRE(!a->direct_dW || (a->splits == 1 && a->chunk_rows == 0 && ((uintptr_t)a->direct_dW % 16) == 0 && !a->bias_ws),
              "%s: direct mode needs splits == 1, no balanced units, a 16-byte aligned dW and no bias slabs", who);
@@ -580,6 +606,7 @@ extern "C" int m3_wgrad_multi(const m3_wgrad_multi_args *a, void *stream) {
     M3_REQUIRE(q.dC && q.A && q.dW, "m3_wgrad_multi: null operand in problem %d", j);
     M3_REQUIRE((q.N * es) % 16 == 0 && (q.K * es) % 16 == 0 && (q.lddc * es) % 16 == 0 && (q.lda * es) % 16 == 0 && q.lddc >= q.N && q.lda >= q.K,
                "m3_wgrad_multi: problem %d: rows and N*elem, K*elem must be multiples of 16 bytes", j);
+    M3_REQUIRE(q.lddc * es < ((int64_t)1 << 32) && q.lda * es < ((int64_t)1 << 32), "m3_wgrad_multi: problem %d: a row stride of 4 GiB or more", j);
     M3_REQUIRE(((uintptr_t)q.dC % 16) == 0 && ((uintptr_t)q.A % 16) == 0 && ((uintptr_t)q.dW % 16) == 0 && ((uintptr_t)q.db % 16) == 0,
                "m3_wgrad_multi: problem %d: alignment", j);
     for (int i = 0; i < j; ++i)

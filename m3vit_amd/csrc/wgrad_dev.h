@@ -92,11 +92,22 @@ __device__ __forceinline__ void wgrad_store_bias(const WgradDev &p, float v, int
 
 // balanced grouped mode: units are dealt to the groups in order, n_g = ceil(rows_g / chunk) each, a group's rows
 // divided evenly over its units (a hot expert gets proportionally more units; the slab of unit u is ws[u]).
+// The two rules of the map, host and device (the kernels below, m3_wgrad_reduce_grouped and the host query m3_wgrad_unit_of
+// all go through them): how many units a group gets, and which of its rows unit j of them covers - equal shares in whole
+// WG_ROWS granules, share = round_up(ceil(rows / n), WG_ROWS) <= chunk (chunk is a multiple of WG_ROWS), so (n - 1) * share
+// <= (n - 1) * chunk < rows: no unit is empty, none is longer than chunk, all but a group's last are whole granules.
+__host__ __device__ __forceinline__ int wgrad_units_of_group(int rows, int chunk) { return (rows + chunk - 1) / chunk; }
+__host__ __device__ __forceinline__ void wgrad_unit_rows(int rows, int n, int j, int &begin, int &end) {
+  const int per = ((rows + n - 1) / n + WG_ROWS - 1) / WG_ROWS * WG_ROWS;
+  begin = j * per;
+  end = begin + per < rows ? begin + per : rows;
+}
+
 // One lane per group (G <= 64): ONE load of the offsets per wave and a shuffle scan instead of G dependent loads.
 // Returns this lane's group's (rows, n, exclusive prefix of n).
 __device__ __forceinline__ void wgrad_unit_scan(const int32_t *off, int G, int chunk, int lane, int &rows, int &n, int &first) {
   rows = lane < G ? off[lane + 1] - off[lane] : 0;
-  n = (rows + chunk - 1) / chunk;
+  n = wgrad_units_of_group(rows, chunk);
   int incl = n;
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
@@ -121,9 +132,10 @@ __device__ __forceinline__ bool wgrad_unit(const int32_t *off, int G, int chunk,
   const unsigned long long m = __ballot(u >= first && u < first + n);
   g = __ffsll((long long)m) - 1;
   rows = __shfl(rows, g, 64); n = __shfl(n, g, 64); first = __shfl(first, g, 64);
-  const int per = ((rows + n - 1) / n + WG_ROWS - 1) / WG_ROWS * WG_ROWS;      // 32-row granules; per <= chunk
-  r0 = (int64_t)off[g] + (int64_t)(u - first) * per;
-  r1 = r0 + per < off[g + 1] ? r0 + per : off[g + 1];
+  int b, e;
+  wgrad_unit_rows(rows, n, u - first, b, e);
+  r0 = (int64_t)off[g] + b;
+  r1 = (int64_t)off[g] + e;
   return true;
 }
 

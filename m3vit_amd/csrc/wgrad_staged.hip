@@ -52,6 +52,24 @@ __device__ __forceinline__ f32x4 read_tr_frag<float>(const char *base, int rb, i
   return f;
 }
 
+// Diagnostic build only (make CXXFLAGS+=-DM3_WGRAD_STAMPS, tools/wgrad_tn_stamps.py): lane 0 of wave 0 of the workgroups of
+// output tile 0 (one per work unit or row part) records s_memtime at entry, after the prologue and four times per 32-row
+// step of the steady-state loop - loads issued, MFMAs issued, LDS stores issued (the step's data has arrived), barrier
+// passed.  -DM3_WGRAD_TN_INDEX_BEHIND additionally restores the former order of the loads (the indices of step s + 1 behind
+// the data of step s), for the before / after timeline.  No stamp executes in the shipped kernel.
+#ifdef M3_WGRAD_STAMPS
+constexpr int WTSTAMP_WGS = 128, WTSTAMP_N = 2 + 4 * 80;
+__device__ unsigned long long g_wtn_stamps[WTSTAMP_WGS][WTSTAMP_N];
+#define WT_STAMP(i)                                                                                                   \
+  do {                                                                                                                \
+    const int wg_ = blockIdx.y + gridDim.y * blockIdx.z;                                                              \
+    if (threadIdx.x == 0 && blockIdx.x == 0 && wg_ < WTSTAMP_WGS && (i) < WTSTAMP_N)                                  \
+      g_wtn_stamps[wg_][(i)] = __builtin_amdgcn_s_memtime();                                                          \
+  } while (0)
+#else
+#define WT_STAMP(i) do { } while (0)
+#endif
+
 // One workgroup's work once it knows what is its own: output tile `tile` of group g over the 32-row steps s_begin .. s_begin +
 // nst - 1 of the rows r0 .. r1 - 1, result to slab `slab_id` (or into dW: direct mode).  Shared by wgrad_tn_kernel and the
 // batched wgrad_multi_kernel (wgrad_multi.hip).
@@ -97,16 +115,22 @@ __device__ __forceinline__ void wgrad_tile_loop(const WgradDev &p, int tile, int
   const char *c_base = p.dC + (int64_t)ncol * ES;
   const char *a_base = p.A + (int64_t)kcol * ES;
   const int st_off = srow * STRIDE + c * 16;                // + i*RSTEP*STRIDE
-  const int64_t rbase = r0 + s_begin * ROWS + srow;      // row of chunk 0 in local step 0
+  // Rows and row strides in 32 bits (M < 2^31 and strides below 4 GiB: the entry points check both), so that a row's byte
+  // offset is ONE 32 x 32 -> 64-bit multiply-add onto the base.  As int64_t row * int64_t stride every address was three
+  // quarter-rate multiplies + the add, four addresses per half step: half of the time between a barrier and the last load
+  // request of a plain-row launch (profiles/expert_wgrad_units.txt).
+  const uint32_t ldc = (uint32_t)p.lddc_b, lda = (uint32_t)p.lda_b;
+  const uint32_t rbase = (uint32_t)(r0 + s_begin * ROWS + srow);      // row of chunk 0 in local step 0
+  const uint32_t rend = (uint32_t)r1;
 
-  auto row_of = [&](int step, int i) -> int64_t {           // clamped slot row
-    int64_t m = rbase + (int64_t)step * ROWS + i * RSTEP;
-    return m < r1 ? m : r1 - 1;
+  auto row_of = [&](int step, int i) -> uint32_t {          // clamped slot row (called with nst > 0 only: r1 > r0 >= 0)
+    const uint32_t m = rbase + (uint32_t)(step * ROWS + i * RSTEP);
+    return m < rend ? m : rend - 1;
   };
   auto load_index = [&](int step, int32_t(&ic)[NLD], int32_t(&ia)[NLD]) {
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-      const int64_t m = row_of(step, i);
+      const uint32_t m = row_of(step, i);
       if (GC) ic[i] = p.c_row_idx[m];
       if (GA) ia[i] = p.a_row_idx[m];
     }
@@ -116,11 +140,11 @@ __device__ __forceinline__ void wgrad_tile_loop(const WgradDev &p, int tile, int
                          float(&rs)[NLD]) {
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-      const int64_t m = row_of(step, i);
-      const int64_t cr = GC ? (int64_t)div_by(ic[i], p.c_row_div, p.c_row_sh) : m;
-      const int64_t ar = GA ? (int64_t)div_by(ia[i], p.a_row_div, p.a_row_sh) : m;
-      rc[i] = *(const u32x4 *)(c_base + cr * p.lddc_b);
-      ra[i] = *(const u32x4 *)(a_base + ar * p.lda_b);
+      const uint32_t m = row_of(step, i);
+      const uint32_t cr = GC ? (uint32_t)div_by(ic[i], p.c_row_div, p.c_row_sh) : m;
+      const uint32_t ar = GA ? (uint32_t)div_by(ia[i], p.a_row_div, p.a_row_sh) : m;
+      rc[i] = *(const u32x4 *)(c_base + (uint64_t)cr * ldc);
+      ra[i] = *(const u32x4 *)(a_base + (uint64_t)ar * lda);
       if (SC) rs[i] = p.c_row_scale[ic[i]];
     }
   };
@@ -128,7 +152,7 @@ __device__ __forceinline__ void wgrad_tile_loop(const WgradDev &p, int tile, int
     char *base = smem + buf * (2 * OPB) + st_off;
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-      const bool ok = rbase + (int64_t)step * ROWS + i * RSTEP < r1;
+      const bool ok = rbase + (uint32_t)(step * ROWS + i * RSTEP) < rend;
       const u32x4 cv = SC ? scale_chunk<T>(rc[i], rs[i]) : rc[i];
       *(u32x4 *)(base + i * RSTEP * STRIDE) = ok ? cv : u32x4{0u, 0u, 0u, 0u};
       *(u32x4 *)(base + i * RSTEP * STRIDE + OPB) = ok ? ra[i] : u32x4{0u, 0u, 0u, 0u};
@@ -165,40 +189,65 @@ __device__ __forceinline__ void wgrad_tile_loop(const WgradDev &p, int tile, int
     }
   };
 
+  WT_STAMP(0);                                    // entry
   if (nst > 0) {
-    // prefetch distance 2 for the data (two register sets), 3 for the gather indices; steps past the
-    // end re-load the last step (clamped) so that nothing in the steady-state loop is conditional.
+    // prefetch distance 2 for the data (two register sets) and 4 for the gather indices (two sets: even and odd steps);
+    // steps past the end re-load the last step (clamped) so that nothing in the steady-state loop is conditional.
+    // A half step requests the data of step s through its index set and then re-loads that set with the indices of step
+    // s + 2.  Memory operations retire in order, so the wait for an index stands for everything requested before it: here
+    // that is data the LDS stores of the half step before have waited for already, and the index has had a whole step to
+    // arrive.  (One index set, re-loaded behind the data of step s with the indices of step s + 1 and used half a step
+    // later, made the first gathered row address of every half step wait for the data requested just before it - one step
+    // of data in flight instead of two, and half a step for the index: profiles/expert_wgrad_units.txt.)
     const int last = nst - 1;
     auto cl = [&](int s_) { return s_ < last ? s_ : last; };
     u32x4 rc0[NLD], ra0[NLD], rc1[NLD], ra1[NLD];
     float sc0[NLD], sc1[NLD];
-    int32_t ic[NLD], ia[NLD];
-    load_index(0, ic, ia);
-    load_global(0, ic, ia, rc1, ra1, sc1);
-    load_index(cl(1), ic, ia);
-    load_global(cl(1), ic, ia, rc0, ra0, sc0);
-    load_index(cl(2), ic, ia);
+    int32_t ic0[NLD], ia0[NLD], ic1[NLD], ia1[NLD];
+    // (ic, ia): the set of step ds, (jc, ja): the other one
+    auto fetch = [&](int ds, int32_t(&ic)[NLD], int32_t(&ia)[NLD], u32x4(&rc)[NLD], u32x4(&ra)[NLD], float(&rs)[NLD],
+                     int32_t(&jc)[NLD], int32_t(&ja)[NLD]) {
+      load_global(ds, ic, ia, rc, ra, rs);
+#if defined(M3_WGRAD_STAMPS) && defined(M3_WGRAD_TN_INDEX_BEHIND)
+      load_index(cl(ds + 1), jc, ja);             // the former order, for the timeline it is compared with
+#else
+      load_index(cl(ds + 2), ic, ia);
+#endif
+    };
+    load_index(0, ic0, ia0);
+    load_index(cl(1), ic1, ia1);
+    load_global(0, ic0, ia0, rc1, ra1, sc1);
+    load_index(cl(2), ic0, ia0);
+    load_global(cl(1), ic1, ia1, rc0, ra0, sc0);
+    load_index(cl(3), ic1, ia1);
     store_lds(0, 0, rc1, ra1, sc1);
     __syncthreads();
-    // entry of even local step t: buf0 = tile t, set0 = tile t+1, (ic, ia) = indices of tile t+2
+    WT_STAMP(1);                                  // step 0 in LDS
+    // entry of even local step t: buf0 = tile t, set0 = tile t+1, (ic0, ia0) / (ic1, ia1) = indices of tiles t+2 / t+3
     int t = 0;
     for (; t + 3 < nst; t += 2) {
-      load_global(t + 2, ic, ia, rc1, ra1, sc1);
-      load_index(cl(t + 3), ic, ia);
+      fetch(t + 2, ic0, ia0, rc1, ra1, sc1, ic1, ia1);
       __builtin_amdgcn_sched_barrier(0);
+      WT_STAMP(2 + 4 * t);                        // loads issued (the wait for the indices is over)
       compute(0);
+      WT_STAMP(3 + 4 * t);                        // MFMAs issued
       store_lds(1, t + 1, rc0, ra0, sc0);
+      WT_STAMP(4 + 4 * t);                        // the step's data has arrived and is in LDS
       __syncthreads();
-      load_global(t + 3, ic, ia, rc0, ra0, sc0);
-      load_index(cl(t + 4), ic, ia);
+      WT_STAMP(5 + 4 * t);                        // barrier passed
+      fetch(t + 3, ic1, ia1, rc0, ra0, sc0, ic0, ia0);
       __builtin_amdgcn_sched_barrier(0);
+      WT_STAMP(6 + 4 * t);
       compute(1);
+      WT_STAMP(7 + 4 * t);
       store_lds(0, t + 2, rc1, ra1, sc1);
+      WT_STAMP(8 + 4 * t);
       __syncthreads();
+      WT_STAMP(9 + 4 * t);
     }
     const int rem = nst - t;
     if (rem == 3) {
-      load_global(t + 2, ic, ia, rc1, ra1, sc1);
+      load_global(t + 2, ic0, ia0, rc1, ra1, sc1);
       compute(0);
       store_lds(1, t + 1, rc0, ra0, sc0);
       __syncthreads();
@@ -285,3 +334,17 @@ int launch_wgrad_staged(int dtype, bool gc, bool ga, bool sc, dim3 grid, const W
 }
 
 }  // namespace m3
+
+#ifdef M3_WGRAD_STAMPS
+extern "C" int m3_debug_wtn_stamps(unsigned long long *dst, int wgs, int clear) {
+  using namespace m3;
+  if (wgs > WTSTAMP_WGS) wgs = WTSTAMP_WGS;
+  const size_t bytes = (size_t)wgs * WTSTAMP_N * sizeof(unsigned long long);
+  if (dst && hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_wtn_stamps), bytes) != hipSuccess) return M3_ERR_LAUNCH;
+  if (clear) {
+    void *sym = nullptr;
+    if (hipGetSymbolAddress(&sym, HIP_SYMBOL(g_wtn_stamps)) != hipSuccess || hipMemset(sym, 0, sizeof(g_wtn_stamps)) != hipSuccess) return M3_ERR_LAUNCH;
+  }
+  return M3_OK;
+}
+#endif
