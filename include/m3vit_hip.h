@@ -625,6 +625,16 @@ int m3_assemble_tokens(const float *patch, const float *cls, const float *pos, i
  * dpos f32 [np+1, D] (+)= sum_b dtok[b] ; dcls f32 [D] (+)= sum_b dtok[b,0]  (beta 0/1). */
 int m3_tokens_bwd(const float *dtok, int B, int np_, int D, void *dpatch, int dtype, float *dpos,
                   float *dcls, int beta, void *stream);
+/* The same pair with TWO prefix tokens in front of the patches - a distilled model's cls and distillation token,
+ * vision_transformer_moe.py:784-790: tokens[b,0,:] = cls + pos[0] ; tokens[b,1,:] = dist + pos[1] ;
+ * tokens[b,2+i,:] = patch[b*np+i,:] + pos[2+i]  (fp32 out; pos f32 [np+2, D]).  cls and dist are separate [D] vectors
+ * anywhere in memory.  Backward: dpatch (act dtype, may be NULL) [B*np, D] = dtok[:,2:,:] ; dpos f32 [np+2, D] (+)=
+ * sum_b dtok[b] ; dcls (+)= sum_b dtok[b,0] ; ddist (+)= sum_b dtok[b,1]  (beta 0/1), summed in the order m3_tokens_bwd
+ * uses (the same kernel body): the same bits from run to run.  D % 4 == 0. */
+int m3_assemble_tokens2(const float *patch, const float *cls, const float *dist, const float *pos, int B, int np_, int D,
+                        float *tokens, void *stream);
+int m3_tokens_bwd2(const float *dtok, int B, int np_, int D, void *dpatch, int dtype, float *dpos, float *dcls,
+                   float *ddist, int beta, void *stream);
 
 /* ------------------------------------------------------------- optimizer tail
  * What every trainer of the reference runs behind the backward (GradScaler.unscale_, clip_grad_norm_, scaler.step of
@@ -908,6 +918,30 @@ int m3_loss_softce_fwd(const void *logits, int dtype, const float *target, const
 int m3_loss_softce_bwd(const void *logits, int dtype, const float *target, const int64_t *label, double smoothing,
                        const float *lse, const float *tsum, const void *record, const float *grad_out, int B, int C,
                        void *dlogits, void *stream);
+/* The teacher term of the distillation loss (pretrain/models/losses.py:50-68) on the student's distillation logits [B,C] and the
+ * teacher's logits [B,C], each M3_F32 / M3_F16 / M3_BF16 with a dtype code of its own (a teacher under autocast returns 16 bits
+ * while the student's head returns fp32); 1 <= C <= M3_SOFTCE_MAX_C, B*C < 2^31 - 2^20, finite inputs.
+ *   M3_DISTILL_SOFT: loss = tau^2 / (B C) sum_i [ sum_c q_ic (t_ic - x_ic) / tau - lse(t_i / tau) + lse(x_i / tau) ], q =
+ *     softmax(t / tau): kl_div(log_softmax(x / tau), log_softmax(t / tau), "sum", log_target) tau^2 / numel (:53-60).
+ *     COEF = tau / (B C);  dlogits = (softmax(x / tau) - q) * COEF * *grad_out.
+ *   M3_DISTILL_HARD: loss = (1 / B) sum_i [ lse(x_i) - x_i[y_i] ], y_i = argmax_c t_ic, ties to the lowest index
+ *     (m3_cls_eval_update's rule) - cross_entropy(x, t.argmax(1)) (:61-64); tau is not read.
+ *     COEF = 1 / B;  dlogits = (softmax(x_i) - onehot(y_i)) * COEF * *grad_out.
+ * Both lse values use running maxima (finite at |x| / tau = 6e4).  The forward writes per row lse f32 [B], the student's, and aux,
+ * B four-byte words: the teacher's lse (f32, soft) or y_i (int32, hard); the backward reads them and, hard, not the teacher's
+ * logits (teacher may be NULL there).  ws: m3_distill_ws_elems(B) floats, no initialisation.  record: the M3_LOSS_REC_WORDS
+ * words (VALUE, COEF, N_VALID B).  Forward: one workgroup per row, then one workgroup that adds the rows in order in double; no
+ * float atomics, nothing read back, the same bits from run to run.  grad_out: DEVICE f32.  dlogits has the logits' dtype.
+ * 16-byte accesses where logits / teacher / dlogits are 16-byte aligned and C % 4 == 0 (both fp32) or C % 8 == 0 (one of them
+ * 16-bit); the scalar path otherwise. */
+#define M3_DISTILL_SOFT 0
+#define M3_DISTILL_HARD 1
+int64_t m3_distill_ws_elems(int B);
+int m3_loss_distill_fwd(const void *logits, int dtype, const void *teacher, int teacher_dtype, int kind, double tau, int B, int C,
+                        float *lse, void *aux, float *ws, void *record, void *stream);
+int m3_loss_distill_bwd(const void *logits, int dtype, const void *teacher, int teacher_dtype, int kind, double tau,
+                        const float *lse, const void *aux, const void *record, const float *grad_out, int B, int C,
+                        void *dlogits, void *stream);
 /* One batch of the evaluation loop (pretrain/engine/evaluate.py:29-37) ADDED to state, M3_CLS_EVAL_WORDS 8-byte words: f64
  * LOSS_SUM, CORRECT1, CORRECT5, COUNT - the vector evaluate.py:44-50 all-reduces - then int64 N_BAD.  Per row the plain cross-
  * entropy lse - x[y] and rank = #{c : x_c > x_y} + #{c < y : x_c == x_y} (ties to the lower index; a NaN logit beats every

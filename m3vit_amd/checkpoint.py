@@ -196,15 +196,17 @@ def adapt_gates(state, multi_gate: bool, num_tasks: int, extra_gate_rows: int = 
     return out
 
 
-def resize_pos_embed(pos_embed: torch.Tensor, grid_hw: Tuple[int, int], align_corners: bool = False) -> torch.Tensor:
-    """[1, 1 + h0*w0, C] -> [1, 1 + h*w, C]: cls row kept, the patch grid resized bilinearly"""
+def resize_pos_embed(pos_embed: torch.Tensor, grid_hw: Tuple[int, int], align_corners: bool = False,
+                     num_prefix: int = 1) -> torch.Tensor:
+    """[1, num_prefix + h0*w0, C] -> [1, num_prefix + h*w, C]: the prefix rows (cls; cls and dist of a distilled model:
+    num_prefix=2) kept, the patch grid resized bilinearly"""
     n, tokens, c = pos_embed.shape
-    side = int(round((tokens - 1) ** 0.5))
-    if side * side != tokens - 1:
-        raise ValueError(f"pos_embed with {tokens - 1} patch positions is not a square grid")
-    grid = pos_embed[:, 1:].transpose(1, 2).reshape(n, c, side, side)
+    side = int(round((tokens - num_prefix) ** 0.5))
+    if side * side != tokens - num_prefix:
+        raise ValueError(f"pos_embed with {tokens - num_prefix} patch positions is not a square grid")
+    grid = pos_embed[:, num_prefix:].transpose(1, 2).reshape(n, c, side, side)
     grid = torch.nn.functional.interpolate(grid, size=tuple(grid_hw), mode="bilinear", align_corners=align_corners)
-    return torch.cat((pos_embed[:, :1], grid.reshape(n, c, -1).transpose(1, 2)), dim=1)
+    return torch.cat((pos_embed[:, :num_prefix], grid.reshape(n, c, -1).transpose(1, 2)), dim=1)
 
 
 def to_backbone_state(checkpoint, rank: int = 0, world_size: int = 1, expected_global_experts: Optional[int] = None,
@@ -216,8 +218,9 @@ def to_backbone_state(checkpoint, rank: int = 0, world_size: int = 1, expected_g
     state = OrderedDict((strip_wrapper_prefix(k), v) for k, v in state.items() if torch.is_tensor(v))
     fmt = infer_expert_format(ck, state, expected_global_experts, world_size)
     state = adapt_gates(state, multi_gate, num_tasks, extra_gate_rows)
-    if grid_hw is not None and "pos_embed" in state and state["pos_embed"].shape[1] != 1 + grid_hw[0] * grid_hw[1]:
-        state["pos_embed"] = resize_pos_embed(state["pos_embed"], grid_hw)
+    num_prefix = 2 if "dist_token" in state else 1                     # a distilled model: cls and dist rows in front
+    if grid_hw is not None and "pos_embed" in state and state["pos_embed"].shape[1] != num_prefix + grid_hw[0] * grid_hw[1]:
+        state["pos_embed"] = resize_pos_embed(state["pos_embed"], grid_hw, num_prefix=num_prefix)
     if world_size > 1 and fmt != "local":
         d0 = first_expert_dim0(state)
         if d0 is not None:

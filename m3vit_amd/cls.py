@@ -9,9 +9,12 @@ expressed as `act_dtype=torch.float16` (fp16 activations into the MFMA GEMMs, fp
 accumulation, fp32 master weights) - the custom autograd Functions pick their dtypes themselves, so a
 surrounding `torch.autocast` context is harmless and not needed.
 
-Out of scope here as in the reference's own hot path: distillation token / head_dist, DeiT warm start
-(network fetch).  Mixup / CutMix, the soft-target criteria, the EMA and the evaluation sums of the same trainer
-are in m3vit_amd/pretrain.py."""
+`MoEViTConfig(distilled=True)` (:97,207-212) adds the distillation token to the encoder and a second head,
+`head_dist`, on token row 1: training returns "logits" as the pair (logits_cls, logits_dist) that
+`pretrain.DistillationLoss` takes, evaluation returns their mean.
+
+Out of scope: the DeiT warm start (network fetch).  Mixup / CutMix, the soft-target criteria, the distillation
+loss, the EMA and the evaluation sums of the same trainer are in m3vit_amd/pretrain.py."""
 from dataclasses import dataclass
 import math
 
@@ -64,8 +67,6 @@ class HipLinear(nn.Linear):
 class MoEViTForImageNet(nn.Module):
     def __init__(self, cfg: MoEViTConfig, act_dtype=torch.float32):
         super().__init__()
-        if cfg.distilled:
-            raise NotImplementedError("distillation token / head_dist are outside the hot path")
         if not cfg.random_init:
             raise NotImplementedError("DeiT warm start needs a network fetch; load a state_dict instead")
         self.cfg = cfg
@@ -78,16 +79,24 @@ class MoEViTForImageNet(nn.Module):
             moe_experts=cfg.moe_experts, moe_top_k=cfg.moe_top_k, world_size=cfg.world_size, gate_dim=cfg.gate_dim,
             moe_gate_type=cfg.moe_gate_type, vmoe_noisy_std=cfg.vmoe_noisy_std,
             gate_task_specific_dim=cfg.gate_task_specific_dim, multi_gate=cfg.multi_gate, num_tasks=-1,
-            use_checkpointing=cfg.use_checkpointing, act_dtype=act_dtype, random_init=cfg.random_init)
+            use_checkpointing=cfg.use_checkpointing, act_dtype=act_dtype, random_init=cfg.random_init,
+            distilled=cfg.distilled)
         self.norm = nn.LayerNorm(cfg.embed_dim)                       # eps = 1e-5 (nn.LayerNorm default, :97)
         self.head = HipLinear(cfg.embed_dim, cfg.num_classes)
         self.head.act_dtype = act_dtype
-        self.head_dist = None
+        self.head_dist = HipLinear(cfg.embed_dim, cfg.num_classes) if cfg.distilled else None      # :97
         nn.init.trunc_normal_(self.head.weight, std=0.02)
         nn.init.zeros_(self.head.bias)
+        if self.head_dist is not None:                                # :100-102
+            self.head_dist.act_dtype = act_dtype
+            nn.init.trunc_normal_(self.head_dist.weight, std=0.02)
+            nn.init.zeros_(self.head_dist.bias)
 
     def no_weight_decay(self):
-        return {"encoder.pos_embed", "encoder.cls_token"}
+        no_wd = {"encoder.pos_embed", "encoder.cls_token"}
+        if self.head_dist is not None:
+            no_wd.add("encoder.dist_token")
+        return no_wd
 
     def forward(self, x):
         tokens, cv_loss = self.encoder(x)
@@ -95,10 +104,20 @@ class MoEViTForImageNet(nn.Module):
             raise RuntimeError(f"Expected token output [B, N, C], got shape {tuple(tokens.shape)}")
         # LayerNorm is per row and only the cls row feeds the head: normalise that row alone (same value and
         # gradient as norm(tokens)[:, 0], :189-190)
-        cls = LayerNormFn.apply(tokens[:, 0].contiguous(), self.norm.weight, self.norm.bias, self.norm.eps,
+        if self.head_dist is None:
+            cls = LayerNormFn.apply(tokens[:, 0].contiguous(), self.norm.weight, self.norm.bias, self.norm.eps,
+                                    self.act_dtype)
+            logits_cls = self.head(cls).float()
+            return {"logits": logits_cls, "cv_loss": cv_loss}
+        if tokens.shape[1] < 2:
+            raise RuntimeError(f"Distilled model expects [cls, dist, ...] tokens, got shape {tuple(tokens.shape)}")
+        # rows 0 (cls) and 1 (dist) feed the two heads: one LayerNorm call on the [B, 2, D] slice (:207-212)
+        pre = LayerNormFn.apply(tokens[:, :2].contiguous(), self.norm.weight, self.norm.bias, self.norm.eps,
                                 self.act_dtype)
-        logits_cls = self.head(cls).float()
-        return {"logits": logits_cls, "cv_loss": cv_loss}
+        logits_cls = self.head(pre[:, 0].contiguous()).float()
+        logits_dist = self.head_dist(pre[:, 1].contiguous()).float()
+        logits = (logits_cls, logits_dist) if self.training else (logits_cls + logits_dist) / 2
+        return {"logits": logits, "cv_loss": cv_loss}
 
 
 def amp_train_step(model, criterion, optimizer, scaler, samples, targets, moe_cv_weight=0.01, clip_grad=None):
@@ -110,7 +129,7 @@ def amp_train_step(model, criterion, optimizer, scaler, samples, targets, moe_cv
     loss = criterion(samples, logits, targets)
     cv = None
     if cv_loss is not None:
-        cv = cv_loss.mean() if torch.is_tensor(cv_loss) else torch.tensor(float(cv_loss), device=logits.device)
+        cv = cv_loss.mean() if torch.is_tensor(cv_loss) else torch.tensor(float(cv_loss), device=samples.device)
         loss = loss + moe_cv_weight * cv
     loss_value = loss.item()
     if not math.isfinite(loss_value):

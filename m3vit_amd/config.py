@@ -15,8 +15,9 @@ import torch
 class BackboneConfig:
     def __init__(self, img_size=(224, 224), patch_size=16, in_chans=3, embed_dim=384, depth=12, num_heads=12,
                  mlp_ratio=4.0, moe_mlp_ratio=1.0, moe_experts=16, moe_top_k=4, gate_dim=386, multi_gate=True,
-                 gate_task_specific_dim=-1, vmoe_noisy_std=0.0, dense_only=False):
+                 gate_task_specific_dim=-1, vmoe_noisy_std=0.0, dense_only=False, distilled=False):
         self.dense_only = dense_only
+        self.distilled = bool(distilled)                   # a distillation token behind cls (vision_transformer_moe.py:602,627-629)
         self.img_size = tuple(img_size)
         self.patch_size = patch_size
         self.in_chans = in_chans
@@ -38,7 +39,7 @@ class BackboneConfig:
 
     @property
     def num_tokens(self):
-        return (self.img_size[0] // self.patch_size) * (self.img_size[1] // self.patch_size) + 1
+        return (self.img_size[0] // self.patch_size) * (self.img_size[1] // self.patch_size) + 1 + int(self.distilled)
 
     @property
     def d_gate(self):
@@ -55,7 +56,7 @@ class BackboneConfig:
         f_attn = self.depth * (2 * N * D * 3 * D + 4 * N * N * D + 2 * N * D * D)
         f_dense = (self.depth - n_moe) * (4 * N * D * Hd)
         f_moe = n_moe * (4 * N * self.moe_top_k * D * Hm + 2 * N * self.d_gate * self.moe_experts)
-        f_patch = 2 * (N - 1) * (self.in_chans * self.patch_size ** 2) * D
+        f_patch = 2 * (N - 1 - int(self.distilled)) * (self.in_chans * self.patch_size ** 2) * D
         return f_attn + f_dense + f_moe + f_patch
 
     def stem_flops_per_image(self):
@@ -64,7 +65,7 @@ class BackboneConfig:
         Hd = int(D * self.mlp_ratio)
         s = next((i for i in range(self.depth) if self.is_moe(i)), self.depth)
         f_block = 2 * N * D * 3 * D + 4 * N * N * D + 2 * N * D * D + 4 * N * D * Hd
-        return s * f_block + 2 * (N - 1) * (self.in_chans * self.patch_size ** 2) * D
+        return s * f_block + 2 * (N - 1 - int(self.distilled)) * (self.in_chans * self.patch_size ** 2) * D
 
 
 VIT_SMALL_MOE = dict(img_size=(224, 224), embed_dim=384, depth=12, num_heads=12, mlp_ratio=4.0, moe_mlp_ratio=1.0,
@@ -89,6 +90,8 @@ def init_params(cfg: BackboneConfig, seed: int = 1, zero_bias: bool = True) -> D
     P = {"patch_embed.proj.weight": _tn((D, cfg.in_chans, cfg.patch_size, cfg.patch_size), .02, g),
          "patch_embed.proj.bias": bias(D),
          "cls_token": _tn((1, 1, D), .02, g), "pos_embed": _tn((1, cfg.num_tokens, D), .02, g)}
+    if cfg.distilled:
+        P["dist_token"] = _tn((1, 1, D), .02, g)
     if cfg.gate_task_specific_dim >= 0 and not cfg.multi_gate:
         # gate_task_represent = new_Mlp(num_tasks, gtsd, gtsd) (vision_transformer_moe.py:638-641, :263-281)
         gt = cfg.gate_task_specific_dim

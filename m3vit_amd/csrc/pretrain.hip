@@ -233,6 +233,179 @@ __global__ __launch_bounds__(PT_THREADS) void softce_bwd_kernel(const T *__restr
   }
 }
 
+// ------------------------------------------------------------------------------------------------ distillation loss
+// pretrain/models/losses.py:50-68 on the student's distillation logits x and the teacher's logits t, each in a dtype of its
+// own.  SOFT: tau^2 / (B C) sum_i [ sum_c q_ic (t_ic - x_ic) / tau - lse(t_i / tau) + lse(x_i / tau) ], q = softmax(t / tau)
+// (kl_div(log p, log q, sum, log_target) tau^2 / numel with sum_c q = 1); hard: (1 / B) sum_i [ lse(x_i) - x_i[y_i] ], y_i the
+// teacher's argmax, ties to the lowest index.  One workgroup per row; the forward leaves per row the student lse and, in aux,
+// the teacher lse (f32) or the argmax (i32), which is all the backward needs of the teacher's side.
+
+// lse of sc * x over one row with a running maximum per thread (row_pass's arithmetic; sc = 1 multiplies exactly)
+template <typename T, int V>
+__device__ __forceinline__ float row_lse_scaled(const T *__restrict__ xr, int C, float sc, float *sh) {
+  const int units = C / V;
+  float m = -INFINITY, s = 0.f;
+  for (int u0 = 0; u0 < units; u0 += PT_THREADS) {
+    const int u = u0 + threadIdx.x;
+    const bool on = u < units;
+    const int e = (on ? u : units - 1) * V;
+    float v[V];
+    Pack<T, V>::load(xr + e, v);
+    if (on) {
+#pragma unroll
+      for (int k = 0; k < V; ++k) v[k] *= sc;
+      float cm = v[0];
+#pragma unroll
+      for (int k = 1; k < V; ++k) cm = fmaxf(cm, v[k]);
+      const float mn = fmaxf(m, cm);
+      float cs = 0.f;
+#pragma unroll
+      for (int k = 0; k < V; ++k) cs += __expf(v[k] - mn);
+      s = __builtin_fmaf(s, __expf(m - mn), cs);
+      m = mn;
+    }
+  }
+  const float M = block_max_f(m, sh);
+  s = m == -INFINITY ? 0.f : s * __expf(m - M);
+  return M + __logf(block_sum_f(s, sh));
+}
+
+// the larger value wins, of equal values the lower index (m3_cls_eval_update's rule)
+__device__ __forceinline__ void argmax_take(float &bv, int &bi, float ov, int oi) {
+  if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+}
+
+// argmax over one row; every thread returns the same index in [0, C)
+template <typename T, int V>
+__device__ __forceinline__ int row_argmax(const T *__restrict__ tr, int C, float *sh, int *shi) {
+  const int units = C / V;
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int u0 = 0; u0 < units; u0 += PT_THREADS) {
+    const int u = u0 + threadIdx.x;
+    const bool on = u < units;
+    const int e = (on ? u : units - 1) * V;
+    float v[V];
+    Pack<T, V>::load(tr + e, v);
+    if (on) {
+#pragma unroll
+      for (int k = 0; k < V; ++k) argmax_take(bv, bi, v[k], e + k);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    argmax_take(bv, bi, ov, oi);
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = bv; shi[threadIdx.x >> 6] = bi; }
+  __syncthreads();
+  bv = sh[0]; bi = shi[0];
+#pragma unroll
+  for (int j = 1; j < 4; ++j) argmax_take(bv, bi, sh[j], shi[j]);
+  return bi < C ? bi : 0;                                              // (a row without a finite maximum: not the contract)
+}
+
+// ws: f32 [B] row terms
+template <typename TX, typename TT, int V, bool SOFT>
+__global__ __launch_bounds__(PT_THREADS) void distill_fwd_kernel(const TX *__restrict__ x, const TT *__restrict__ t, float inv_tau,
+                                                                 int B, int C, float *__restrict__ lse, void *__restrict__ aux,
+                                                                 float *__restrict__ ws) {
+  __shared__ float sh[4];
+  __shared__ int shi[4];
+  for (int row = blockIdx.x; row < B; row += gridDim.x) {
+    const TX *xr = x + (int64_t)row * C;
+    const TT *tr = t + (int64_t)row * C;
+    const float lx = row_lse_scaled<TX, V>(xr, C, SOFT ? inv_tau : 1.f, sh);
+    if (SOFT) {
+      const float lt = row_lse_scaled<TT, V>(tr, C, inv_tau, sh);
+      const int units = C / V;
+      float a = 0.f;
+      for (int u0 = 0; u0 < units; u0 += PT_THREADS) {                  // the row again (it is in the cache): sum q (t - x) / tau
+        const int u = u0 + threadIdx.x;
+        const bool on = u < units;
+        const int e = (on ? u : units - 1) * V;
+        float xv[V], tv[V];
+        Pack<TX, V>::load(xr + e, xv);
+        Pack<TT, V>::load(tr + e, tv);
+        if (on) {
+#pragma unroll
+          for (int k = 0; k < V; ++k) {
+            const float ts = tv[k] * inv_tau, xs = xv[k] * inv_tau;
+            a = __builtin_fmaf(__expf(ts - lt), ts - xs, a);
+          }
+        }
+      }
+      const float dot = block_sum_f(a, sh);
+      if (threadIdx.x == 0) {
+        lse[row] = lx;
+        ((float *)aux)[row] = lt;
+        ws[row] = dot + (lx - lt);
+      }
+    } else {
+      const int y = row_argmax<TT, V>(tr, C, sh, shi);
+      if (threadIdx.x == 0) {
+        lse[row] = lx;
+        ((int32_t *)aux)[row] = y;
+        ws[row] = lx - (float)xr[y];
+      }
+    }
+  }
+}
+
+// one workgroup: the B row terms in row order in double (as softce_finalize_kernel); value = sum * num / den
+__global__ __launch_bounds__(256) void distill_finalize_kernel(const float *__restrict__ ws, int B, double num, double den,
+                                                               float coef, int32_t *__restrict__ rec) {
+  __shared__ double sh_s[256];
+  const int t = threadIdx.x;
+  double s = 0.0;
+  for (int i = t; i < B; i += 256) s += (double)ws[i];
+  sh_s[t] = s;
+  __syncthreads();
+  if (t != 0) return;
+  s = 0.0;
+  for (int i = 0; i < 256; ++i) s += sh_s[i];
+  ((float *)rec)[M3_LOSS_REC_VALUE] = (float)(s * num / den);
+  ((float *)rec)[M3_LOSS_REC_COEF] = coef;
+  ((float *)rec)[M3_LOSS_REC_COEF2] = 0.f;
+  rec[M3_LOSS_REC_N_VALID] = B;
+  rec[M3_LOSS_REC_N_AUX] = 0;
+  rec[M3_LOSS_REC_N_BAD] = 0;
+  rec[6] = rec[7] = 0;
+}
+
+// d x over the flat [B * C] span, V elements of one row per access.  SOFT: (exp(x / tau - lse_x) - exp(t / tau - lse_t)) coef
+// upstream; hard: (exp(x - lse_x) - [c == y]) coef upstream (t is not read)
+template <typename TX, typename TT, int V, bool SOFT>
+__global__ __launch_bounds__(PT_THREADS) void distill_bwd_kernel(const TX *__restrict__ x, const TT *__restrict__ t, float inv_tau,
+                                                                 const float *__restrict__ lse, const void *__restrict__ aux,
+                                                                 const float *__restrict__ rec, const float *__restrict__ gout,
+                                                                 int C, int units, TX *__restrict__ dx) {
+  const float kf = rec[M3_LOSS_REC_COEF] * *gout;
+  for (int u0 = blockIdx.x * PT_THREADS; u0 < units; u0 += gridDim.x * PT_THREADS) {
+    const int u = u0 + threadIdx.x;
+    const bool on = u < units;
+    const uint32_t e = (uint32_t)(on ? u : units - 1) * V, row = e / (uint32_t)C;
+    const int c0 = (int)(e - row * (uint32_t)C);
+    float xv[V], d[V];
+    Pack<TX, V>::load(x + e, xv);
+    const float lx = lse[row];
+    if (SOFT) {
+      float tv[V];
+      Pack<TT, V>::load(t + e, tv);
+      const float lt = ((const float *)aux)[row];
+#pragma unroll
+      for (int k = 0; k < V; ++k) d[k] = (__expf(xv[k] * inv_tau - lx) - __expf(tv[k] * inv_tau - lt)) * kf;
+    } else {
+      const int y = ((const int32_t *)aux)[row];
+#pragma unroll
+      for (int k = 0; k < V; ++k) d[k] = (__expf(xv[k] - lx) - (c0 + k == y ? 1.f : 0.f)) * kf;
+    }
+    if (on) Pack<TX, V>::store(dx + e, d);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ evaluation update
 // Per row: plain cross-entropy lse - x[y], and the rank of the target logit = #{c : x_c beats x_y}: a larger value beats, an
 // equal value at a lower index beats, a NaN beats every number and an earlier NaN beats a later one (meter.hip's argmax rule).
@@ -358,6 +531,29 @@ template <typename F> static inline void by_vec_form(bool vec, bool dense, F &&f
   else { if (dense) f(IntTag<1>{}, IntTag<1>{}); else f(IntTag<1>{}, IntTag<0>{}); }
 }
 
+static int distill_args_ok(const void *x, int x_dtype, int t_dtype, int kind, double tau, int B, int C, const char *who) {
+  M3_REQUIRE(B >= 1 && C >= 1 && C <= M3_SOFTCE_MAX_C, "%s: B = %d, C = %d: B >= 1 and 1 <= C <= %d", who, B, C, M3_SOFTCE_MAX_C);
+  M3_REQUIRE(dtype_ok(x_dtype) && dtype_ok(t_dtype), "%s: bad dtype code %d / %d", who, x_dtype, t_dtype);
+  M3_REQUIRE((int64_t)B * C < ((int64_t)1 << 31) - ((int64_t)1 << 20), "%s: %lld elements: the kernels index with 32 bits", who,
+             (long long)B * C);
+  M3_REQUIRE(kind == M3_DISTILL_SOFT || kind == M3_DISTILL_HARD, "%s: bad kind %d", who, kind);
+  M3_REQUIRE(kind == M3_DISTILL_HARD || (tau > 0.0 && tau <= 3.0e38), "%s: tau %g must be positive and finite", who, tau);
+  M3_REQUIRE(x != nullptr, "%s: null logits", who);
+  return 0;
+}
+
+// f(DtypeTag<TX>{}, DtypeTag<TT>{}, IntTag<V>{}): V = 1, or the 16-byte width of the pair - 4 elements when both are fp32, 8 as
+// soon as one of them has 16 bits (C % V == 0 keeps every row of either on a 16-byte boundary)
+template <typename F> static inline void by_distill_form(int x_dtype, int t_dtype, bool vec, F &&f) {
+  by_dtype(x_dtype, [&](auto tx) {
+    by_dtype(t_dtype, [&](auto tt) {
+      constexpr int W = (sizeof(typename decltype(tx)::type) == 4 && sizeof(typename decltype(tt)::type) == 4) ? 4 : 8;
+      if (vec) f(tx, tt, IntTag<W>{}); else f(tx, tt, IntTag<1>{});
+    });
+  });
+}
+static inline int distill_width(int x_dtype, int t_dtype) { return (x_dtype == M3_F32 && t_dtype == M3_F32) ? 4 : 8; }
+
 }  // namespace m3
 
 using namespace m3;
@@ -439,6 +635,58 @@ extern "C" int m3_loss_softce_bwd(const void *logits, int dtype, const float *ta
     });
   });
   return check_launch("m3_loss_softce_bwd");
+}
+
+extern "C" int64_t m3_distill_ws_elems(int B) { return B < 1 ? 0 : (int64_t)B; }
+
+extern "C" int m3_loss_distill_fwd(const void *logits, int dtype, const void *teacher, int teacher_dtype, int kind, double tau,
+                                   int B, int C, float *lse, void *aux, float *ws, void *record, void *stream) {
+  if (int rc = distill_args_ok(logits, dtype, teacher_dtype, kind, tau, B, C, "m3_loss_distill_fwd")) return rc;
+  M3_REQUIRE(teacher && lse && aux && ws && record, "m3_loss_distill_fwd: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const bool soft = kind == M3_DISTILL_SOFT;
+  const bool vec = C % distill_width(dtype, teacher_dtype) == 0 && aligned16(logits) && aligned16(teacher);
+  const float inv_tau = soft ? (float)(1.0 / tau) : 1.f;
+  const int nblk = B < LS_MAX_BLOCKS ? B : LS_MAX_BLOCKS;
+  by_distill_form(dtype, teacher_dtype, vec, [&](auto tx, auto tt, auto v) {
+    typedef typename decltype(tx)::type TX;
+    typedef typename decltype(tt)::type TT;
+    auto go = [&](auto f) {
+      hipLaunchKernelGGL((distill_fwd_kernel<TX, TT, decltype(v)::value, decltype(f)::value != 0>), dim3(nblk), dim3(PT_THREADS), 0,
+                         s, (const TX *)logits, (const TT *)teacher, inv_tau, B, C, lse, aux, ws);
+    };
+    if (soft) go(IntTag<1>{}); else go(IntTag<0>{});
+  });
+  if (int rc = check_launch("m3_loss_distill_fwd (rows)")) return rc;
+  const double den = soft ? (double)B * (double)C : (double)B;
+  hipLaunchKernelGGL(distill_finalize_kernel, dim3(1), dim3(256), 0, s, ws, B, soft ? tau * tau : 1.0, den,
+                     (float)((soft ? tau : 1.0) / den), (int32_t *)record);
+  return check_launch("m3_loss_distill_fwd (finalize)");
+}
+
+extern "C" int m3_loss_distill_bwd(const void *logits, int dtype, const void *teacher, int teacher_dtype, int kind, double tau,
+                                   const float *lse, const void *aux, const void *record, const float *grad_out, int B, int C,
+                                   void *dlogits, void *stream) {
+  if (int rc = distill_args_ok(logits, dtype, teacher_dtype, kind, tau, B, C, "m3_loss_distill_bwd")) return rc;
+  const bool soft = kind == M3_DISTILL_SOFT;
+  M3_REQUIRE(lse && aux && record && grad_out && dlogits && (teacher || !soft), "m3_loss_distill_bwd: null pointer");
+  if (!soft) teacher_dtype = dtype;                                     // the teacher's logits are not read: one instance per TX
+  const int W = distill_width(dtype, teacher_dtype);
+  const bool vec = C % W == 0 && aligned16(logits) && aligned16(dlogits) && (!soft || aligned16(teacher));
+  const float inv_tau = soft ? (float)(1.0 / tau) : 1.f;
+  const int units = (int)((int64_t)B * C / (vec ? W : 1));
+  const int nblk = blocks_for(units, PT_THREADS);
+  by_distill_form(dtype, teacher_dtype, vec, [&](auto tx, auto tt, auto v) {
+    typedef typename decltype(tx)::type TX;
+    typedef typename decltype(tt)::type TT;
+    auto go = [&](auto f) {
+      hipLaunchKernelGGL((distill_bwd_kernel<TX, TT, decltype(v)::value, decltype(f)::value != 0>), dim3(nblk), dim3(PT_THREADS), 0,
+                         (hipStream_t)stream, (const TX *)logits, (const TT *)teacher, inv_tau, lse, aux, (const float *)record,
+                         grad_out, C, units, (TX *)dlogits);
+    };
+    if (soft) go(IntTag<1>{}); else go(IntTag<0>{});
+  });
+  return check_launch("m3_loss_distill_bwd");
 }
 
 extern "C" int64_t m3_cls_eval_ws_elems(int B) { return B < 1 ? 0 : 4 * (int64_t)B; }

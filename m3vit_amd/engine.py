@@ -95,7 +95,10 @@ class BackboneEngine(ExpertParallelMixin):
         self.P = cfg.patch_size
         self.hp, self.wp = cfg.img_size[0] // self.P, cfg.img_size[1] // self.P
         self.np_ = self.hp * self.wp
-        self.N = self.np_ + 1
+        # a distilled model (vision_transformer_moe.py:602,627-629) carries a distillation token behind cls: told by the
+        # parameters, not by cfg (the oracle's BackboneCfg has no such field)
+        self.distilled = "dist_token" in (share.params if share is not None else params)
+        self.N = self.np_ + (2 if self.distilled else 1)
         self.T = self.B * self.N
         self.E = cfg.moe_experts
         self.k = cfg.moe_top_k
@@ -542,7 +545,11 @@ class BackboneEngine(ExpertParallelMixin):
     def _embed(self, images):
         ops.im2row(images, self.P, self.rows)
         ops.gemm_nt(self.rows, self.wc["patch_embed.proj"], self.patch, bias=self.params["patch_embed.proj.bias"])
-        ops.assemble_tokens(self.patch, self.params["cls_token"], self.params["pos_embed"], self.B, self.np_, self.D, self.x0)
+        p = self.params
+        if self.distilled:
+            ops.assemble_tokens2(self.patch, p["cls_token"], p["dist_token"], p["pos_embed"], self.B, self.np_, self.D, self.x0)
+        else:
+            ops.assemble_tokens(self.patch, p["cls_token"], p["pos_embed"], self.B, self.np_, self.D, self.x0)
         return self.x0
 
     # The forward in resumable pieces (patch embedding / one block at a time / result), so that a step runner can
@@ -822,7 +829,11 @@ class BackboneEngine(ExpertParallelMixin):
         dx = self._bw["dx"]
         if stem:
             # patch embedding / cls / pos
-            ops.tokens_bwd(dx, B, self.np_, D, self.s_dpatch, gr["pos_embed"].view(self.N, D), gr["cls_token"].view(D), beta=1)
+            if self.distilled:
+                ops.tokens_bwd2(dx, B, self.np_, D, self.s_dpatch, gr["pos_embed"].view(self.N, D), gr["cls_token"].view(D),
+                                gr["dist_token"].view(D), beta=1)
+            else:
+                ops.tokens_bwd(dx, B, self.np_, D, self.s_dpatch, gr["pos_embed"].view(self.N, D), gr["cls_token"].view(D), beta=1)
             gw = gr["patch_embed.proj.weight"].view(D, -1)
             self._fork((), lambda: ops.wgrad_tn(self.s_dpatch, self.rows, gw, beta=1, ws=self.ws_wgrad, queue=self.wq,
                                                 db=gr["patch_embed.proj.bias"]))

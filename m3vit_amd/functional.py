@@ -397,6 +397,28 @@ class SoftCrossEntropyFn(torch.autograd.Function):
         return ops.loss_softce_bwd(x, tgt, lse, tsum, record, _upstream(g), ctx.smoothing), None, None
 
 
+class DistillLossFn(torch.autograd.Function):
+    """pretrain/models/losses.py:50-68: the teacher term of the distillation loss on the student's distillation logits and the
+    teacher's logits (csrc/pretrain.hip: m3_loss_distill_fwd / _bwd); kind "soft" (KL at temperature tau) or "hard"
+    (cross-entropy against the teacher's argmax).  Saves the rows' log-sum-exp and the teacher's side per row; the teacher's
+    logits get no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, teacher, kind, tau):
+        x = logits.contiguous()
+        t = teacher.detach().contiguous()
+        record, lse, aux = ops.loss_distill_fwd(x, t, kind, tau)
+        ctx.save_for_backward(x, t, record, lse, aux)
+        ctx.kind, ctx.tau = kind, tau
+        ctx.mark_non_differentiable(record)
+        return _loss_value(record), record
+
+    @staticmethod
+    def backward(ctx, g, _g_record):
+        x, t, record, lse, aux = ctx.saved_tensors
+        return ops.loss_distill_bwd(x, t, ctx.kind, lse, aux, record, _upstream(g), ctx.tau), None, None, None
+
+
 class MaskedL1Fn(torch.autograd.Function):
     """losses/loss_functions.py:126-140 (DepthLoss('l1'))"""
 

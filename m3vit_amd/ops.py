@@ -9,6 +9,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import gc
+import math
 import os
 from ctypes import byref, c_void_p
 from typing import Optional
@@ -1419,6 +1420,81 @@ def loss_softce_bwd(logits, target, lse, tsum, record, grad_out, smoothing=0.0, 
     return dlogits
 
 
+DISTILL_KINDS = {"soft": _lib.M3_DISTILL_SOFT, "hard": _lib.M3_DISTILL_HARD}
+
+
+def distill_ws_elems(B: int) -> int:
+    return int(lib().m3_distill_ws_elems(B))
+
+
+def _distill_args(logits, teacher, kind, tau):
+    """(B, C, kind code) of a distillation-loss call; teacher None: not read (the hard backward)"""
+    B, C = _dims(logits, 2, "logits")
+    _act(logits, "logits")
+    if B < 1 or not 1 <= C <= _lib.M3_SOFTCE_MAX_C:
+        raise _lib.M3Error(f"logits must be [B >= 1, 1 <= C <= {_lib.M3_SOFTCE_MAX_C}], got {tuple(logits.shape)}")
+    if B * C >= 2 ** 31 - 2 ** 20:
+        raise _lib.M3Error(f"{B * C} logits: the kernels index with 32 bits")
+    if kind not in DISTILL_KINDS:
+        raise _lib.M3Error(f"kind must be 'soft' or 'hard', got {kind!r}")
+    if kind == "soft" and not (0.0 < float(tau) < math.inf):
+        raise _lib.M3Error(f"tau must be positive and finite, got {tau}")
+    if teacher is not None:
+        if not isinstance(teacher, torch.Tensor) or tuple(teacher.shape) != (B, C):
+            raise _lib.M3Error(f"teacher logits must have the student's shape {(B, C)}, got "
+                               f"{tuple(teacher.shape) if isinstance(teacher, torch.Tensor) else type(teacher).__name__}")
+        _act(teacher, "teacher", B * C)
+        if teacher.device != logits.device:
+            raise _lib.M3Error(f"teacher logits live on {teacher.device}, the student's on {logits.device}")
+    return B, C, DISTILL_KINDS[kind]
+
+
+def loss_distill_fwd(logits, teacher, kind, tau=1.0, *, lse=None, aux=None, ws=None, record=None):
+    """The teacher term of the distillation loss (m3_loss_distill_fwd): student logits [B, C] and teacher logits [B, C], each
+    fp32 / fp16 / bf16; kind "soft" (KL at temperature tau, scaled tau^2 / (B C)) or "hard" (cross-entropy against the
+    teacher's argmax).  Returns (record, lse, aux): the int32 loss record, the student rows' log-sum-exp and the teacher's
+    side per row (int32 words: the bits of its float32 lse, soft; its argmax, hard), both for the backward."""
+    B, C, code = _distill_args(logits, teacher, kind, tau)
+    if teacher is None:
+        raise _lib.M3Error("teacher logits are required")
+    dev = logits.device
+    need = distill_ws_elems(B)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.float32, device=dev)
+    _req(ws, torch.float32, "ws", min_numel=need)
+    if record is None:
+        record = torch.empty(LOSS_REC_WORDS, dtype=torch.int32, device=dev)
+    _req(record, torch.int32, "record", numel=LOSS_REC_WORDS)
+    if lse is None:
+        lse = torch.empty(B, dtype=torch.float32, device=dev)
+    _req(lse, torch.float32, "lse", numel=B)
+    if aux is None:
+        aux = torch.empty(B, dtype=torch.int32, device=dev)
+    _req(aux, torch.int32, "aux", numel=B)
+    check(lib().m3_loss_distill_fwd(_p(logits), dt_code(logits.dtype), _p(teacher), dt_code(teacher.dtype), code, float(tau), B, C,
+                                    _p(lse), _p(aux), _p(ws), _p(record), _stream()), "m3_loss_distill_fwd")
+    return record, lse, aux
+
+
+def loss_distill_bwd(logits, teacher, kind, lse, aux, record, grad_out, tau=1.0, *, dlogits=None):
+    """d logits of loss_distill_fwd, scaled by the 1-element float32 GPU tensor grad_out (read on the device); in the logits'
+    dtype.  teacher may be None for kind "hard" (the argmax in aux is all that is read of it)."""
+    B, C, code = _distill_args(logits, teacher, kind, tau)
+    if teacher is None and kind == "soft":
+        raise _lib.M3Error("teacher logits are required for kind 'soft'")
+    _req(lse, torch.float32, "lse", numel=B)
+    _req(aux, torch.int32, "aux", numel=B)
+    _req(record, torch.int32, "record", numel=LOSS_REC_WORDS)
+    _req(grad_out, torch.float32, "grad_out", numel=1)
+    if dlogits is None:
+        dlogits = torch.empty_like(logits)
+    _req(dlogits, logits.dtype, "dlogits", numel=B * C)
+    tdt = dt_code(teacher.dtype) if teacher is not None else dt_code(logits.dtype)
+    check(lib().m3_loss_distill_bwd(_p(logits), dt_code(logits.dtype), _p(teacher), tdt, code, float(tau), _p(lse), _p(aux),
+                                    _p(record), _p(grad_out), B, C, _p(dlogits), _stream()), "m3_loss_distill_bwd")
+    return dlogits
+
+
 def cls_eval_ws_elems(B: int) -> int:
     return int(lib().m3_cls_eval_ws_elems(B))
 
@@ -1707,3 +1783,21 @@ def tokens_bwd(dtok, B, np_, D, dpatch, dpos, dcls, beta=0):
         _act(dpatch, "dpatch", B * np_ * D)
     check(lib().m3_tokens_bwd(_p(dtok), B, np_, D, _p(dpatch), dt_code(dpatch.dtype) if dpatch is not None else M3_F32,
                               _p(dpos), _p(dcls), beta, _stream()), "m3_tokens_bwd")
+
+
+def assemble_tokens2(patch, cls, dist, pos, B, np_, D, tokens):
+    """assemble_tokens with two prefix tokens (cls, dist) in front of the patches: a distilled model (m3_assemble_tokens2)"""
+    _req(patch, torch.float32, "patch", B * np_ * D); _req(cls, torch.float32, "cls", D); _req(dist, torch.float32, "dist", D)
+    _req(pos, torch.float32, "pos", (np_ + 2) * D); _req(tokens, torch.float32, "tokens", B * (np_ + 2) * D)
+    check(lib().m3_assemble_tokens2(_p(patch), _p(cls), _p(dist), _p(pos), B, np_, D, _p(tokens), _stream()),
+          "m3_assemble_tokens2")
+    return tokens
+
+
+def tokens_bwd2(dtok, B, np_, D, dpatch, dpos, dcls, ddist, beta=0):
+    _req(dtok, torch.float32, "dtok", B * (np_ + 2) * D); _req(dpos, torch.float32, "dpos", (np_ + 2) * D)
+    _req(dcls, torch.float32, "dcls", D); _req(ddist, torch.float32, "ddist", D)
+    if dpatch is not None:
+        _act(dpatch, "dpatch", B * np_ * D)
+    check(lib().m3_tokens_bwd2(_p(dtok), B, np_, D, _p(dpatch), dt_code(dpatch.dtype) if dpatch is not None else M3_F32,
+                               _p(dpos), _p(dcls), _p(ddist), beta, _stream()), "m3_tokens_bwd2")

@@ -28,7 +28,7 @@ import torch
 
 from . import ops
 
-NO_DECAY = ("bias", "norm", "pos_embed", "cls_token", "w_gate")
+NO_DECAY = ("bias", "norm", "pos_embed", "cls_token", "dist_token", "w_gate")
 
 
 def _round4(n: int) -> int:

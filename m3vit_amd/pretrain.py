@@ -13,7 +13,9 @@ Differences from the reference, all on purpose:
     executor contexts and captured graphs that must not be copied.  It has neither `.module` nor `.ema`, so
     pretrain/utils/checkpoint.py:20-39 falls back to its state_dict() / load_state_dict();
   * CPU tensors raise M3Error: there is no eager fallback.
-Not here: cutmix_minmax, RandomErasing, RandAugment, distillation (cls.py has no distillation token), a CPU-resident EMA.
+Distillation (DistillationLoss 'soft' / 'hard', pretrain/models/losses.py:50-68) runs with a distilled model
+(MoEViTConfig(distilled=True)) and a teacher module the caller supplies.
+Not here: cutmix_minmax, RandomErasing, RandAugment, building a teacher, a CPU-resident EMA.
 """
 from __future__ import annotations
 
@@ -25,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .functional import SoftCrossEntropyFn
+from .functional import DistillLossFn, SoftCrossEntropyFn
 
 __all__ = ["Mixup", "SoftTargetCrossEntropy", "LabelSmoothingCrossEntropy", "CrossEntropy", "DistillationLoss",
            "build_criterion", "ClsEvalMeter", "ModelEma", "pretrain_step"]
@@ -176,16 +178,22 @@ class CrossEntropy(LabelSmoothingCrossEntropy):
 
 
 class DistillationLoss(nn.Module):
-    """pretrain/models/losses.py:8-74 with distillation_type 'none' - the only one a model without a distillation token can
-    run.  forward(inputs, outputs, labels) -> base_criterion(outputs, labels).  last_stats keeps the reference's keys
-    (loss_base, loss_distill, loss_no_cv); the losses in it are 0-dim DEVICE tensors that become floats when a reader
-    converts them (float(v), a logger's .item()) - the reference calls .item() every step."""
+    """pretrain/models/losses.py:8-74.  forward(inputs, outputs, labels): 'none' -> base_criterion(outputs, labels); 'soft' /
+    'hard' -> base * (1 - alpha) + distill * alpha, where outputs is the (class logits, distillation logits) pair a distilled
+    model returns in training, the teacher runs on `inputs` under no_grad and the teacher term is one kernel pair
+    (m3_loss_distill_fwd / _bwd: KL at temperature tau scaled tau^2 / numel, or cross-entropy against the teacher's argmax).
+    The teacher is any nn.Module that maps the inputs to [B, C] logits on the GPU (fp32, fp16 or bf16).
+    last_stats keeps the reference's keys (loss_base, loss_distill, loss_no_cv); the losses in it are 0-dim DEVICE tensors
+    that become floats when a reader converts them (float(v), a logger's .item()) - the reference calls .item() every step.
+    'soft' / 'hard' without a teacher is refused here; the reference would fail at the first forward, on None(inputs)."""
 
     def __init__(self, base_criterion, teacher_model, distillation_type, alpha, tau):
         super().__init__()
-        if distillation_type != "none":
-            raise NotImplementedError(f"DistillationLoss: distillation_type {distillation_type!r} needs a distillation token, "
-                                      "which MoEViTForImageNet does not have; only 'none' is supported")
+        if distillation_type not in ("none", "soft", "hard"):
+            raise ValueError(f"DistillationLoss: distillation_type must be 'none', 'soft' or 'hard', got {distillation_type!r}")
+        if distillation_type != "none" and teacher_model is None:
+            raise NotImplementedError(f"DistillationLoss: distillation_type {distillation_type!r} needs a teacher_model; "
+                                      "building one (timm.create_model) is the caller's")
         self.base_criterion = base_criterion
         self.teacher_model = teacher_model
         self.distillation_type = distillation_type
@@ -194,12 +202,23 @@ class DistillationLoss(nn.Module):
         self.last_stats = {}
 
     def forward(self, inputs, outputs, labels):
+        outputs_kd = None
         if isinstance(outputs, tuple):
-            outputs = outputs[0]
+            outputs, outputs_kd = outputs
         base_loss = self.base_criterion(outputs, labels)
-        d = base_loss.detach()
-        self.last_stats = {"loss_base": d, "loss_distill": 0.0, "loss_no_cv": d}
-        return base_loss
+        if self.distillation_type == "none":
+            d = base_loss.detach()
+            self.last_stats = {"loss_base": d, "loss_distill": 0.0, "loss_no_cv": d}
+            return base_loss
+        if outputs_kd is None:
+            raise ValueError("Distillation is enabled but model did not return distillation logits. "
+                             "Either disable distillation or add a distillation head.")
+        with torch.no_grad():
+            teacher_outputs = self.teacher_model(inputs)
+        distill_loss, _ = DistillLossFn.apply(outputs_kd, teacher_outputs, self.distillation_type, float(self.tau))
+        total = base_loss * (1 - self.alpha) + distill_loss * self.alpha
+        self.last_stats = {"loss_base": base_loss.detach(), "loss_distill": distill_loss.detach(), "loss_no_cv": total.detach()}
+        return total
 
 
 def build_criterion(args, teacher_model=None):
@@ -359,7 +378,7 @@ def pretrain_step(model, criterion, optimizer, scaler, samples, targets, mixup_f
     loss = criterion(samples, logits, targets)
     cv = None
     if cv_loss is not None:
-        cv = cv_loss.mean() if torch.is_tensor(cv_loss) else torch.tensor(float(cv_loss), device=logits.device)
+        cv = cv_loss.mean() if torch.is_tensor(cv_loss) else torch.tensor(float(cv_loss), device=samples.device)
         loss = loss + moe_cv_weight * cv
     optimizer.zero_grad(set_to_none=True)
     scaler.scale(loss).backward()

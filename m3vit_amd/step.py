@@ -104,7 +104,7 @@ class MultiTaskStep:
         # the gradient add runs under the stem's backward on the (then idle) first task stream: no stream of its own
         self.add_stream = self.streams[0] if self.share_stem else None
         self.late_names = [n for n in self.eng.params if self.eng._block_of(n) < 0 and
-                           not n.startswith(("patch_embed.", "cls_token", "pos_embed"))]
+                           not n.startswith(("patch_embed.", "cls_token", "dist_token", "pos_embed"))]
         # the part whose block range first reaches below the stem boundary takes the other passes' d x
         self.accept_part = next((j for j, (_, lo) in enumerate(self.block_ranges) if lo < self.stem), len(self.block_ranges) - 1)
         # hipGraph capture: expert-parallel steps read split sizes on the host (eager).  Weight-gradient streams capture

@@ -4,7 +4,8 @@ module names, state_dict keys and forward signatures, running on the HIP kernels
 
 Scope notes: drop / attn_drop must be 0 (as in every BASELINE config), drop_path is supported (torch-level per-sample
 scaling of the residual branches, as pretrain/configs/deit_moe_small.yaml uses it); pretrained
-weight loading, hybrid backbones, distilled tokens and the sem regularisers are out of scope (SURVEY.md section 8);
+weight loading, hybrid backbones and the sem regularisers are out of scope; distilled=True adds the
+distillation token behind cls (:602,627-629,784-790: `dist_token`, a `pos_embed` of patches + 2 rows) on both paths;
 the routing statistics the reference logs to wandb are there (`moe_stats=True`: `latest_moe_stats`, device-side, read lazily).  `forward` returns (tokens [B,N,D], total_cv_loss) like :882-886.
 
 convention="origin" (ctor flag of VisionTransformerMoE / Block, handed down to the layer and the gate) selects the API
@@ -288,7 +289,7 @@ class VisionTransformerMoE(nn.Module):
                  multi_gate=False, regu_experts_fromtask=False, num_experts_pertask=-1, num_tasks=-1,
                  gate_input_ahead=False, expert_prune=False, use_checkpointing=False, act_dtype=torch.float32,
                  random_init=True, sem_force=False, convention="ckpt", fused="auto", fused_grads="auto", moe_stats=False,
-                 **kwargs):
+                 distilled=False, **kwargs):
         """fused: "auto" (default) / True - forward(x, task_id) runs as ONE autograd node on the straight-line executor
         (m3vit_amd/fused.py: hipGraph replay, the parameters' .grad are views of its flat gradient buffer) whenever the call
         is one it covers, and through the per-op autograd Functions below otherwise (`fused_fallback_reason` says why);
@@ -329,7 +330,7 @@ class VisionTransformerMoE(nn.Module):
                                 moe_experts=moe_experts * world_size, moe_top_k=moe_top_k,     # the gate scores all E_loc * W experts
                                 gate_dim=gate_dim if gate_dim >= 0 else embed_dim,
                                 multi_gate=bool(multi_gate), gate_task_specific_dim=gate_task_specific_dim,
-                                vmoe_noisy_std=float(vmoe_noisy_std))
+                                vmoe_noisy_std=float(vmoe_noisy_std), distilled=bool(distilled))
         why = None
         if drop_rate > 0.0:
             why = "element-wise dropout (drop_rate > 0)"
@@ -358,8 +359,9 @@ class VisionTransformerMoE(nn.Module):
         self.patch_embed = PatchEmbed(self.img_size, patch_size, in_chans, embed_dim)
         self.num_patches = self.patch_embed.num_patches
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
-        self.dist_token = None
-        self.pos_embed = nn.Parameter(torch.zeros(1, self.num_patches + 1, embed_dim))
+        self.num_token = 2 if distilled else 1                                         # :602
+        self.dist_token = nn.Parameter(torch.zeros(1, 1, embed_dim)) if distilled else None
+        self.pos_embed = nn.Parameter(torch.zeros(1, self.num_patches + self.num_token, embed_dim))
         self.pos_drop = Dropout(drop_rate, "pos")
         self.num_tasks = gate_dim - embed_dim
         self.gate_task_specific_dim = gate_task_specific_dim
@@ -390,6 +392,8 @@ class VisionTransformerMoE(nn.Module):
     def init_weights(self):
         nn.init.trunc_normal_(self.pos_embed, std=.02)
         nn.init.trunc_normal_(self.cls_token, std=.02)
+        if self.dist_token is not None:                                               # :682-683
+            nn.init.trunc_normal_(self.dist_token, std=.02)
         for _, m in self.named_modules():
             if isinstance(m, nn.Linear):
                 nn.init.trunc_normal_(m.weight, std=.02)
@@ -398,6 +402,12 @@ class VisionTransformerMoE(nn.Module):
             elif isinstance(m, nn.LayerNorm):
                 nn.init.constant_(m.bias, 0)
                 nn.init.constant_(m.weight, 1.0)
+
+    def no_weight_decay(self):                                                        # :735-740
+        no_wd = {"pos_embed", "cls_token"}
+        if self.dist_token is not None:
+            no_wd.add("dist_token")
+        return no_wd
 
     def _forward_fused(self, x, task_id, grads):
         from .fused import FusedBackbone
@@ -432,7 +442,10 @@ class VisionTransformerMoE(nn.Module):
                 raise RuntimeError(f"VisionTransformerMoE(fused=True): {self.fused_fallback_reason}")
         B = x.shape[0]
         x = self.patch_embed(x, self.act_dtype).float()
-        x = self.pos_drop(torch.cat((self.cls_token.expand(B, -1, -1), x), dim=1) + self.pos_embed)      # :791
+        prefix = (self.cls_token.expand(B, -1, -1),)
+        if self.dist_token is not None:                                               # :784-790
+            prefix += (self.dist_token.expand(B, -1, -1),)
+        x = self.pos_drop(torch.cat(prefix + (x,), dim=1) + self.pos_embed)           # :791
         tsf = None
         if (task_id is not None) and (self.gate_task_represent is not None):
             one_hot = torch.zeros(self.num_tasks, device=x.device)
@@ -480,7 +493,7 @@ class VisionTransformerMoE(nn.Module):
                 if moe:
                     rows = torch.stack([blk._stats_rec for _, blk in moe]).cpu().tolist()
                     blocks = {i: blk._parse_stats(r) for (i, blk), r in zip(moe, rows)}
-                    N = self.num_patches + 1
+                    N = self.num_patches + self.num_token
                     B = blocks[moe[0][0]]["gate_token_count"] // N
                     self._stats_cache = (blocks, _ms.aggregate([blocks[i] for i in sorted(blocks)], B * max(N - 1, 0)))
         return self._stats_cache

@@ -14,6 +14,13 @@ algorithmic: mix reads and writes every image once, 8 B per element; EMA reads t
 Last, the whole pretrain_step with the recipe (Mixup + SoftTargetCrossEntropy + ModelEma) and without it (hard labels through
 torch's nn.CrossEntropyLoss, no mixing, no EMA).
     python tools/pretrain_bench.py [--iters 20] [--rounds 5] [--batch 128] [--out profiles/pretrain_step.txt]
+--distill runs another leg INSTEAD (the default output is unchanged): the distillation criterion (m3_loss_distill_fwd / _bwd
+through pretrain.DistillLossFn, soft at tau 3 and hard, fp32 student logits under fp16 teacher logits) beside the reference's
+formula in stock torch ops (pretrain/models/losses.py:53-64), forward + backward; and the whole pretrain_step of a distilled
+model (N = 198, hard distillation against a mean-pool + Linear teacher) beside the non-distilled one (N = 197) and the
+distilled model without the teacher term (criterion 'none': what the second token and head cost by themselves), all with
+Mixup + SoftTargetCrossEntropy + ModelEma.
+    python tools/pretrain_bench.py --distill [--out profiles/distill_step.txt]
 """
 import argparse
 import os
@@ -53,14 +60,112 @@ def ring(make, count):
     return nxt
 
 
+def report(times, header):
+    """median GPU / host ms per row and the rounds' GPU times; returns {name: (GPU ms, host ms)}"""
+    med, lines = {}, header + ["", f"{'':62s} {'GPU ms':>9s} {'host ms':>9s}   GPU ms by round"]
+    for name, v in times.items():
+        gs, hs = sorted(x[0] for x in v), sorted(x[1] for x in v)
+        med[name] = (gs[len(gs) // 2], hs[len(hs) // 2])
+        lines.append(f"{name:62s} {med[name][0]:9.3f} {med[name][1]:9.3f}   " + " ".join(f"{x[0]:.3f}" for x in v))
+    return med, lines
+
+
+def distill_leg(args):
+    from types import SimpleNamespace as NS
+    from m3vit_amd import pretrain
+    from m3vit_amd.cls import MoEViTConfig, MoEViTForImageNet
+    from m3vit_amd.functional import DistillLossFn
+    from m3vit_amd.optim import FusedAdamW
+    dev = torch.device("cuda")
+    B, C, tau = args.batch, 1000, 3.0
+    g = torch.Generator(device="cuda").manual_seed(1)
+    logits = torch.randn(B, C, device=dev, generator=g) * 3
+    teacher_logits = (torch.randn(B, C, device=dev, generator=g) * 3).half()
+
+    def ours(kind):
+        def run():
+            x = logits.detach().requires_grad_(True)
+            DistillLossFn.apply(x, teacher_logits, kind, tau)[0].backward()
+        return run
+
+    def torch_soft():
+        x = logits.detach().requires_grad_(True)
+        (F.kl_div(F.log_softmax(x / tau, dim=1), F.log_softmax(teacher_logits / tau, dim=1), reduction="sum", log_target=True)
+         * (tau * tau) / x.numel()).backward()
+
+    def torch_hard():
+        x = logits.detach().requires_grad_(True)
+        F.cross_entropy(x, teacher_logits.argmax(dim=1)).backward()
+
+    pieces = {"distill soft: m3_loss_distill fwd + bwd": ours("soft"), "distill soft: torch kl_div(log_softmax, log_softmax)": torch_soft,
+              "distill hard: m3_loss_distill fwd + bwd": ours("hard"), "distill hard: torch cross_entropy(x, t.argmax(1))": torch_hard}
+
+    class Teacher(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.fc = torch.nn.Linear(3, C)
+
+        def forward(self, x):
+            return self.fc(x.mean((2, 3))).half()
+
+    if not args.no_step:
+        img_bytes = B * 3 * 224 * 224 * 4
+        images = ring(lambda: torch.randn(B, 3, 224, 224, device=dev, generator=g), max(2, -(-320 * 2 ** 20 // img_bytes)))
+        labels = torch.randint(0, C, (B,), device=dev, generator=g)
+        base = dict(mixup=0.8, cutmix=1.0, smoothing=0.1, cutmix_minmax=None, distillation_alpha=0.5, distillation_tau=1.0)
+        np.random.seed(0)
+        mix = pretrain.Mixup(mixup_alpha=0.8, cutmix_alpha=1.0, label_smoothing=0.1, num_classes=C)
+
+        def step_of(distilled, kind):
+            model = MoEViTForImageNet(MoEViTConfig(distilled=distilled), act_dtype=torch.float16).to(dev).train()
+            opt = FusedAdamW(model.parameters(), lr=1e-4, weight_decay=0.05, max_grad_norm=1.0)
+            scaler = torch.amp.GradScaler("cuda", init_scale=1024.0)
+            crit = pretrain.build_criterion(NS(distillation_type=kind, **base),
+                                            teacher_model=Teacher().to(dev).eval() if kind != "none" else None)
+            ema = pretrain.ModelEma(model, decay=0.9999)
+            return lambda: pretrain.pretrain_step(model, crit, opt, scaler, images(), labels, mixup_fn=mix, model_ema=ema,
+                                                  clip_grad=1.0)
+        pieces["step: distilled (N = 198), hard distillation + recipe"] = step_of(True, "hard")
+        pieces["step: not distilled (N = 197), recipe"] = step_of(False, "none")
+        pieces["step: distilled (N = 198), recipe, no teacher term"] = step_of(True, "none")
+
+    times = {name: [] for name in pieces}
+    for _ in range(args.rounds):
+        for name, fn in pieces.items():
+            times[name].append(timed(fn, max(3, args.iters // 4) if name.startswith("step") else args.iters))
+    med, lines = report(times, [f"distillation at configs[1]: batch {B}, {C} classes, fp32 student logits, fp16 teacher logits, tau {tau:g}; "
+                                f"{args.rounds} alternating rounds x {args.iters} iterations (whole step: {max(3, args.iters // 4)})",
+                                f"device: {torch.cuda.get_device_name(0)}"])
+    lines.append("")
+    names = list(pieces)
+    for o, t in ((names[0], names[1]), (names[2], names[3])):
+        lines.append(f"{o:62s} GPU {med[t][0] / med[o][0]:6.2f}x, host {med[t][1] / med[o][1]:6.2f}x against the stock form")
+    if not args.no_step:
+        a, b = med[names[4]], med[names[5]]
+        c = med[names[6]]
+        lines.append(f"whole step: {a[0]:.3f} ms distilled, {b[0]:.3f} ms not distilled: {a[0] - b[0]:+.3f} ms GPU "
+                     f"({100 * (a[0] / b[0] - 1):+.2f} %), {a[1] - b[1]:+.3f} ms host; of that the second token and head alone "
+                     f"(distilled model, criterion 'none'): {c[0] - b[0]:+.3f} ms GPU ({100 * (c[0] / b[0] - 1):+.2f} %)")
+    text = "\n".join(lines)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--no-step", action="store_true", help="leave out the whole-step rows")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pretrain_step.txt"))
+    ap.add_argument("--distill", action="store_true", help="the distillation leg instead (criterion and distilled step)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "distill_step.txt" if args.distill else "pretrain_step.txt")
+    if args.distill:
+        return distill_leg(args)
     from m3vit_amd import ops, pretrain
     from m3vit_amd.cls import MoEViTConfig, MoEViTForImageNet
     from m3vit_amd.optim import FusedAdamW
