@@ -13,6 +13,11 @@ constexpr int WG_ROWS = 64;      // granule of the row splits (= the largest per
 constexpr int WG_THREADS = 256;
 constexpr int BG_T = 256, BG_THREADS = 512, BG_RS = 512;
 
+// The register-staged kernel's gather table (wgrad_staged.hip): pieces of WG_TAB_ROWS rows, one row per thread, two slots;
+// three arrays of 4-byte entries behind the operand images - source row of dC, per-row factor, source row of A
+constexpr int WG_TAB_ROWS = WG_THREADS;
+constexpr int WG_TAB_BYTES = 3 * 2 * WG_TAB_ROWS * 4;
+
 constexpr int WG_MULTI = 8;     // problems of one batched launch (M3_WGRAD_MULTI_MAX)
 
 // one of the dense slab reductions a batched launch leaves behind (WgradDev.rd_tab)

@@ -55,8 +55,7 @@ __device__ __forceinline__ f32x4 read_tr_frag<float>(const char *base, int rb, i
 // Diagnostic build only (make CXXFLAGS+=-DM3_WGRAD_STAMPS, tools/wgrad_tn_stamps.py): lane 0 of wave 0 of the workgroups of
 // output tile 0 (one per work unit or row part) records s_memtime at entry, after the prologue and four times per 32-row
 // step of the steady-state loop - loads issued, MFMAs issued, LDS stores issued (the step's data has arrived), barrier
-// passed.  -DM3_WGRAD_TN_INDEX_BEHIND additionally restores the former order of the loads (the indices of step s + 1 behind
-// the data of step s), for the before / after timeline.  No stamp executes in the shipped kernel.
+// passed.  No stamp executes in the shipped kernel.
 #ifdef M3_WGRAD_STAMPS
 constexpr int WTSTAMP_WGS = 128, WTSTAMP_N = 2 + 4 * 80;
 __device__ unsigned long long g_wtn_stamps[WTSTAMP_WGS][WTSTAMP_N];
@@ -120,39 +119,103 @@ __device__ __forceinline__ void wgrad_tile_loop(const WgradDev &p, int tile, int
   // quarter-rate multiplies + the add, four addresses per half step: half of the time between a barrier and the last load
   // request of a plain-row launch (profiles/expert_wgrad_units.txt).
   const uint32_t ldc = (uint32_t)p.lddc_b, lda = (uint32_t)p.lda_b;
-  const uint32_t rbase = (uint32_t)(r0 + s_begin * ROWS + srow);      // row of chunk 0 in local step 0
+  const uint32_t rfirst = (uint32_t)(r0 + s_begin * ROWS);            // row 0 of local step 0
+  const uint32_t rbase = rfirst + (uint32_t)srow;                     // row of chunk 0 in local step 0
   const uint32_t rend = (uint32_t)r1;
 
   auto row_of = [&](int step, int i) -> uint32_t {          // clamped slot row (called with nst > 0 only: r1 > r0 >= 0)
     const uint32_t m = rbase + (uint32_t)(step * ROWS + i * RSTEP);
     return m < rend ? m : rend - 1;
   };
-  auto load_index = [&](int step, int32_t(&ic)[NLD], int32_t(&ia)[NLD]) {
+  // The gather table (GC / GA): what a gathered row needs - its source row, index already divided, and with SC its factor -
+  // is loaded ONCE per row and workgroup and kept in LDS behind the operand images, in pieces of WG_TAB_ROWS rows (8 steps),
+  // thread r owning row r of a piece, two slots: the entry of local row l is l mod 2 * WG_TAB_ROWS.  Rows past r1 clamp to
+  // r1 - 1 (their data is zeroed at the LDS store).  (The 16 threads of a row each loaded the row's index and factor
+  // themselves before: two index and two factor loads per thread and step in the queue of the data loads -
+  // profiles/wgrad_steady_loop.txt.)  A piece is made in three stages:
+  //   request (index -> ti), factor (c_row_scale[ti] -> tf), write (rows and factor -> LDS, published by the next barrier).
+  // The prologue makes the pieces 0 and 1; the loop over whole pieces (four pairs of steps, unrolled: every stage at a fixed
+  // place, no branch - behind a branch hipcc copies ti / tf where the paths join, and the copy of a register just loaded is a
+  // wait for everything in flight) makes piece j + 2 while it computes piece j: request and factor at the START of the pairs
+  // 0 and 1, in front of their data loads, so that waiting for them drains only loads the LDS stores have waited for
+  // already; write in the middle of pair 3, behind the barrier after which nobody reads piece j any more.  When that loop
+  // ends, at most 10 steps are left and their two pieces are in the table.
+  constexpr int TMASK = 2 * WG_TAB_ROWS - 1;
+  static_assert(WG_TAB_ROWS % ROWS == 0 && WG_TAB_ROWS / ROWS == 8, "a piece is four pairs of steps");
+  uint32_t *tab_c = (uint32_t *)(smem + 2 * (2 * OPB));
+  float *tab_f = (float *)(tab_c + 2 * WG_TAB_ROWS);
+  uint32_t *tab_a = (uint32_t *)(tab_f + 2 * WG_TAB_ROWS);
+  auto tab_request = [&](int piece, int32_t &xc, int32_t &xa) {
+    uint32_t m = rfirst + (uint32_t)(piece * WG_TAB_ROWS + tid);
+    m = m < rend ? m : rend - 1;
+    if (GC) xc = p.c_row_idx[m];
+    if (GA) xa = p.a_row_idx[m];
+  };
+  auto tab_factor = [&](int32_t xc, float &f) {
+    if (SC) f = p.c_row_scale[xc];
+  };
+  auto tab_write_rows = [&](int piece, int32_t xc, int32_t xa) {
+    const int e = (piece & 1) * WG_TAB_ROWS + tid;
+    if (GC) tab_c[e] = (uint32_t)div_by(xc, p.c_row_div, p.c_row_sh);
+    if (GA) tab_a[e] = (uint32_t)div_by(xa, p.a_row_div, p.a_row_sh);
+  };
+  auto tab_write_factor = [&](int piece, float f) {
+    if (SC) tab_f[(piece & 1) * WG_TAB_ROWS + tid] = f;
+  };
+  // the source rows / the factors of this thread's chunks of `step` (whose piece is in the table)
+  auto tab_rows = [&](int step, uint32_t(&nc)[NLD], uint32_t(&na)[NLD]) {
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-      const uint32_t m = row_of(step, i);
-      if (GC) ic[i] = p.c_row_idx[m];
-      if (GA) ia[i] = p.a_row_idx[m];
+      const int e = (step * ROWS + srow + i * RSTEP) & TMASK;
+      if (GC) nc[i] = tab_c[e];
+      if (GA) na[i] = tab_a[e];
     }
   };
-  // SC: the per-row factor travels with the row's data (loaded next to it, applied at the LDS store)
-  auto load_global = [&](int step, const int32_t(&ic)[NLD], const int32_t(&ia)[NLD], u32x4(&rc)[NLD], u32x4(&ra)[NLD],
-                         float(&rs)[NLD]) {
+  auto tab_factors = [&](int step, float(&rs)[NLD]) {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i)
+      if (SC) rs[i] = tab_f[(step * ROWS + srow + i * RSTEP) & TMASK];
+  };
+  // Two forms of the load and of the LDS store, chosen at compile time by `whole`.
+  // false_type: any step - rows clamped (row_of), one multiply-add per address, rows past the end zeroed at the store.
+  // true_type: a WHOLE step (all 32 rows below r1: every step of a part but its last) that directly follows the step loaded
+  // before - a plain operand's chunk addresses are the pointers pc / pa, bumped by the loop-invariant ROWS * ld after each
+  // use (no clamp, no multiply: profiles/wgrad_steady_loop.txt), and the store writes the registers as they are.
+  // A gathered operand's address is one multiply-add of its table row (nc / na) in both forms.
+  typedef std::false_type any_step;
+  typedef std::true_type whole_step;
+  const char *pc[NLD], *pa[NLD];
+  const uint64_t bump_c = (uint64_t)ROWS * ldc, bump_a = (uint64_t)ROWS * lda;
+  auto point_at = [&](int step) {                           // pc / pa: the plain-row chunk addresses of `step`
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-      const uint32_t m = row_of(step, i);
-      const uint32_t cr = GC ? (uint32_t)div_by(ic[i], p.c_row_div, p.c_row_sh) : m;
-      const uint32_t ar = GA ? (uint32_t)div_by(ia[i], p.a_row_div, p.a_row_sh) : m;
-      rc[i] = *(const u32x4 *)(c_base + (uint64_t)cr * ldc);
-      ra[i] = *(const u32x4 *)(a_base + (uint64_t)ar * lda);
-      if (SC) rs[i] = p.c_row_scale[ic[i]];
+      const uint32_t m = rbase + (uint32_t)(step * ROWS + i * RSTEP);
+      pc[i] = c_base + (uint64_t)m * ldc;
+      pa[i] = a_base + (uint64_t)m * lda;
     }
   };
-  auto store_lds = [&](int buf, int step, const u32x4(&rc)[NLD], const u32x4(&ra)[NLD], const float(&rs)[NLD]) {
+  auto load_global = [&](auto whole, int step, const uint32_t(&nc)[NLD], const uint32_t(&na)[NLD], u32x4(&rc)[NLD],
+                         u32x4(&ra)[NLD]) {
+    constexpr bool W = decltype(whole)::value;
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const char *cp, *ap;
+      if constexpr (GC) cp = c_base + (uint64_t)nc[i] * ldc;
+      else if constexpr (W) { cp = pc[i]; pc[i] += bump_c; }
+      else cp = c_base + (uint64_t)row_of(step, i) * ldc;
+      if constexpr (GA) ap = a_base + (uint64_t)na[i] * lda;
+      else if constexpr (W) { ap = pa[i]; pa[i] += bump_a; }
+      else ap = a_base + (uint64_t)row_of(step, i) * lda;
+      rc[i] = *(const u32x4 *)cp;
+      ra[i] = *(const u32x4 *)ap;
+    }
+  };
+  auto store_lds = [&](auto whole, int buf, int step, const u32x4(&rc)[NLD], const u32x4(&ra)[NLD], const float(&rs)[NLD]) {
+    constexpr bool W = decltype(whole)::value;
     char *base = smem + buf * (2 * OPB) + st_off;
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
-      const bool ok = rbase + (uint32_t)(step * ROWS + i * RSTEP) < rend;
+      const bool ok = W || rbase + (uint32_t)(step * ROWS + i * RSTEP) < rend;
       const u32x4 cv = SC ? scale_chunk<T>(rc[i], rs[i]) : rc[i];
       *(u32x4 *)(base + i * RSTEP * STRIDE) = ok ? cv : u32x4{0u, 0u, 0u, 0u};
       *(u32x4 *)(base + i * RSTEP * STRIDE + OPB) = ok ? ra[i] : u32x4{0u, 0u, 0u, 0u};
@@ -191,73 +254,124 @@ __device__ __forceinline__ void wgrad_tile_loop(const WgradDev &p, int tile, int
 
   WT_STAMP(0);                                    // entry
   if (nst > 0) {
-    // prefetch distance 2 for the data (two register sets) and 4 for the gather indices (two sets: even and odd steps);
-    // steps past the end re-load the last step (clamped) so that nothing in the steady-state loop is conditional.
-    // A half step requests the data of step s through its index set and then re-loads that set with the indices of step
-    // s + 2.  Memory operations retire in order, so the wait for an index stands for everything requested before it: here
-    // that is data the LDS stores of the half step before have waited for already, and the index has had a whole step to
-    // arrive.  (One index set, re-loaded behind the data of step s with the indices of step s + 1 and used half a step
-    // later, made the first gathered row address of every half step wait for the data requested just before it - one step
-    // of data in flight instead of two, and half a step for the index: profiles/expert_wgrad_units.txt.)
+    // prefetch distance 2 for the data (two register sets); a gathered operand's rows come from the table one fetch ahead
+    // (nc / na: read behind the loads of step s for step s + 1 - an LDS read, not in the queue of the data).  Steps past
+    // the end re-load the last step (clamped) so that nothing in the steady-state loop is conditional but the table stages.
     const int last = nst - 1;
     auto cl = [&](int s_) { return s_ < last ? s_ : last; };
     u32x4 rc0[NLD], ra0[NLD], rc1[NLD], ra1[NLD];
-    float sc0[NLD], sc1[NLD];
-    int32_t ic0[NLD], ia0[NLD], ic1[NLD], ia1[NLD];
-    // (ic, ia): the set of step ds, (jc, ja): the other one
-    auto fetch = [&](int ds, int32_t(&ic)[NLD], int32_t(&ia)[NLD], u32x4(&rc)[NLD], u32x4(&ra)[NLD], float(&rs)[NLD],
-                     int32_t(&jc)[NLD], int32_t(&ja)[NLD]) {
-      load_global(ds, ic, ia, rc, ra, rs);
-#if defined(M3_WGRAD_STAMPS) && defined(M3_WGRAD_TN_INDEX_BEHIND)
-      load_index(cl(ds + 1), jc, ja);             // the former order, for the timeline it is compared with
-#else
-      load_index(cl(ds + 2), ic, ia);
-#endif
+    uint32_t nc[NLD] = {}, na[NLD] = {};
+    float rs[NLD] = {};
+    // (fp32, which spills as it is, with ONE gather: the rows of step ds are read in front of its loads - NLD = 4 rows kept
+    // over a step cost it 16 more bytes of scratch; with both gathers it is the other way round)
+    constexpr bool AHEAD = ES == 2 || (GC && GA);
+    auto fetch = [&](auto whole, int ds, u32x4(&rc)[NLD], u32x4(&ra)[NLD]) {
+      if constexpr (!AHEAD) tab_rows(ds, nc, na);
+      load_global(whole, ds, nc, na, rc, ra);
+      if constexpr (AHEAD) tab_rows(cl(ds + 1), nc, na);
     };
-    load_index(0, ic0, ia0);
-    load_index(cl(1), ic1, ia1);
-    load_global(0, ic0, ia0, rc1, ra1, sc1);
-    load_index(cl(2), ic0, ia0);
-    load_global(cl(1), ic1, ia1, rc0, ra0, sc0);
-    load_index(cl(3), ic1, ia1);
-    store_lds(0, 0, rc1, ra1, sc1);
+    auto store_step = [&](int buf, int step, const u32x4(&rc)[NLD], const u32x4(&ra)[NLD]) {      // outside the loop
+      tab_factors(step, rs);
+      store_lds(any_step(), buf, step, rc, ra, rs);
+    };
+    int32_t ti_c = 0, ti_a = 0;
+    float tf = 0.f;
+    if constexpr (GC || GA) {
+      // pieces 0 and 1: the rows first - the addresses of the steps 0 and 1 wait for them - and the factors, which only
+      // the LDS store of step 0 needs, behind the data requests
+      int32_t t0c = 0, t0a = 0;
+      tab_request(0, t0c, t0a);
+      tab_request(1, ti_c, ti_a);
+      tab_write_rows(0, t0c, t0a);
+      tab_write_rows(1, ti_c, ti_a);
+      float f0 = 0.f;
+      tab_factor(t0c, f0);
+      tab_factor(ti_c, tf);
+      __syncthreads();
+      tab_rows(0, nc, na);
+      fetch(any_step(), 0, rc1, ra1);
+      fetch(any_step(), cl(1), rc0, ra0);
+      if constexpr (SC) {
+        tab_write_factor(0, f0);
+        tab_write_factor(1, tf);
+        __syncthreads();
+      }
+    } else {
+      fetch(any_step(), 0, rc1, ra1);
+      fetch(any_step(), cl(1), rc0, ra0);
+    }
+    store_step(0, 0, rc1, ra1);
     __syncthreads();
     WT_STAMP(1);                                  // step 0 in LDS
-    // entry of even local step t: buf0 = tile t, set0 = tile t+1, (ic0, ia0) / (ic1, ia1) = indices of tiles t+2 / t+3
-    int t = 0;
-    for (; t + 3 < nst; t += 2) {
-      fetch(t + 2, ic0, ia0, rc1, ra1, sc1, ic1, ia1);
+    // entry of even local step t: buf0 = tile t, set0 = tile t+1, (nc, na) = the table rows of tile t+2.
+    // The pair of steps (t, t + 1) fetches the steps t + 2 and t + 3 and stores t + 1 and t + 2.  stage: what it does for
+    // the piece after the next one - 0 nothing, 1 request, 2 factor, 3 write, -1: the stage of the pair's place in its piece,
+    // under branches (fp32)
+    auto two_steps = [&](auto whole, auto stage, int t) {
+      constexpr int ST = decltype(stage)::value;
+      const int piece = (t >> 3) + 2, place = (t >> 1) & 3;
+      if (ST == 1 || (ST < 0 && place == 0)) tab_request(piece, ti_c, ti_a);
+      if (ST == 2 || (ST < 0 && place == 1)) tab_factor(ti_c, tf);
+      fetch(whole, t + 2, rc1, ra1);
+      tab_factors(t + 1, rs);
       __builtin_amdgcn_sched_barrier(0);
-      WT_STAMP(2 + 4 * t);                        // loads issued (the wait for the indices is over)
+      WT_STAMP(2 + 4 * t);                        // loads issued
       compute(0);
       WT_STAMP(3 + 4 * t);                        // MFMAs issued
-      store_lds(1, t + 1, rc0, ra0, sc0);
+      store_lds(whole, 1, t + 1, rc0, ra0, rs);
       WT_STAMP(4 + 4 * t);                        // the step's data has arrived and is in LDS
       __syncthreads();
       WT_STAMP(5 + 4 * t);                        // barrier passed
-      fetch(t + 3, ic1, ia1, rc0, ra0, sc0, ic0, ia0);
+      if (ST == 3 || (ST < 0 && place == 3)) {
+        tab_write_rows(piece, ti_c, ti_a);
+        tab_write_factor(piece, tf);
+      }
+      fetch(whole, t + 3, rc0, ra0);
+      tab_factors(t + 2, rs);
       __builtin_amdgcn_sched_barrier(0);
       WT_STAMP(6 + 4 * t);
       compute(1);
       WT_STAMP(7 + 4 * t);
-      store_lds(0, t + 2, rc1, ra1, sc1);
+      store_lds(whole, 0, t + 2, rc1, ra1, rs);
       WT_STAMP(8 + 4 * t);
       __syncthreads();
       WT_STAMP(9 + 4 * t);
+    };
+    typedef std::integral_constant<int, 0> no_stage;
+    // The steady part: while the steps up to t + 3 are whole (t + 3 < last); the fetches run two steps ahead of the
+    // compute, so it ends two steps before the part does and at most one clamped pair and the remainder follow it.
+    // 16-bit instances only: fp32 has NLD = 4, and its eight pointers go to scratch (+4 .. +12 bytes per lane over the
+    // clamped loop, which already spills there), and so do the four unrolled pairs (+12); fp32 keeps the clamped forms for
+    // every step and takes the table stages under branches.
+    int t = 0;
+    if constexpr (ES == 2) point_at(2);
+    if constexpr ((GC || GA) && ES == 2) {        // whole pieces, all of their steps whole, with the table stages
+      for (; t + 10 < nst; t += 8) {
+        two_steps(whole_step(), std::integral_constant<int, 1>(), t);
+        two_steps(whole_step(), std::integral_constant<int, 2>(), t + 2);
+        two_steps(whole_step(), no_stage(), t + 4);
+        two_steps(whole_step(), std::integral_constant<int, 3>(), t + 6);
+      }
     }
+    if constexpr (ES == 2)
+      for (; t + 4 < nst; t += 2) two_steps(whole_step(), no_stage(), t);
+    // (fp32 with a gather: ONE loop, staged to the end - a write happens in the fourth pair of a piece only, and if that pair
+    // runs, the part's last step - all that clamped fetches read - lies in the next piece)
+    typedef std::integral_constant<int, (GC || GA) && ES != 2 ? -1 : 0> tail_stage;
+    for (; t + 3 < nst; t += 2) two_steps(any_step(), tail_stage(), t);
     const int rem = nst - t;
     if (rem == 3) {
-      load_global(t + 2, ic0, ia0, rc1, ra1, sc1);
+      fetch(any_step(), t + 2, rc1, ra1);
       compute(0);
-      store_lds(1, t + 1, rc0, ra0, sc0);
+      store_step(1, t + 1, rc0, ra0);
       __syncthreads();
       compute(1);
-      store_lds(0, t + 2, rc1, ra1, sc1);
+      store_step(0, t + 2, rc1, ra1);
       __syncthreads();
       compute(0);
     } else if (rem == 2) {
       compute(0);
-      store_lds(1, t + 1, rc0, ra0, sc0);
+      store_step(1, t + 1, rc0, ra0);
       __syncthreads();
       compute(1);
     } else {
@@ -322,15 +436,19 @@ struct WgStaged {
 };
 
 int launch_wgrad_staged(int dtype, bool gc, bool ga, bool sc, dim3 grid, const WgradDev &d, hipStream_t s) {
+  // the two operand images of both buffers and, for the instances that gather, the table behind them: 36 / 66 KiB (16-bit /
+  // fp32) + 6 KiB, two workgroups per CU in either case
   const size_t lds16 = 4 * WgLds<half_t>::ROWS * WgLds<half_t>::STRIDE, lds32 = 4 * WgLds<float>::ROWS * WgLds<float>::STRIDE;
+  static_assert(2 * (4 * WgLds<float>::ROWS * WgLds<float>::STRIDE + WG_TAB_BYTES) <= 160 * 1024, "two workgroups per CU");
   static bool attr_set = false;
-  if (!attr_set) {                               // both images exceed the 64 KiB a launch gets without asking
+  if (!attr_set) {                               // the fp32 images exceed the 64 KiB a launch gets without asking
     wgrad_each_instance<WgStaged>([&](int dt, bool, bool, bool, const void *k) {
-      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(dt == M3_F32 ? lds32 : lds16));
+      (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((dt == M3_F32 ? lds32 : lds16) + WG_TAB_BYTES));
     });
     attr_set = true;
   }
-  return wgrad_launch_instance<WgStaged>(dtype, gc, ga, sc, grid, dim3(WG_THREADS), dtype == M3_F32 ? lds32 : lds16, d, s);
+  const size_t lds = (dtype == M3_F32 ? lds32 : lds16) + (gc || ga ? WG_TAB_BYTES : 0);
+  return wgrad_launch_instance<WgStaged>(dtype, gc, ga, sc, grid, dim3(WG_THREADS), lds, d, s);
 }
 
 }  // namespace m3

@@ -4,14 +4,14 @@ rows, 16 experts, N = K = 384 -> 3 / 2368 / 58), operands streamed through a rin
 of the library the in-kernel timeline of the steady-state loop from s_memtime stamps.
 
     (cd m3vit_amd/csrc && make CXXFLAGS="-O3 -fPIC -std=c++17 --offload-arch=gfx950 -DM3_WGRAD_STAMPS" \
-         OBJDIR=../../build/wstamps OUT=../libm3vit_hip_wstamps.so)          # add -DM3_WGRAD_TN_INDEX_BEHIND for the former load order
+         OBJDIR=../../build/wstamps OUT=../libm3vit_hip_wstamps.so)
     M3VIT_LIB=$PWD/m3vit_amd/libm3vit_hip_wstamps.so python tools/wgrad_tn_stamps.py [fc1|fc2|plain ...]
 
 fc1: A rows gathered through a_row_idx / 4.  fc2: dC rows gathered through c_row_idx / 4 and scaled by c_row_scale, fused bias
 gradient.  plain: the same groups and units on plain rows (no index, no factor).  The slot map is the router's: every token
 picks 4 of 16 experts, slots sorted by expert, token order inside an expert.  Stamped: lane 0 of wave 0 of the workgroup of
-output tile 0 of every unit; per 32-row step, cycles from the previous barrier to "loads issued" (contains the wait for the
-gather indices), "MFMAs issued", "LDS stores issued" (contains the wait for the step's data), "barrier passed"."""
+output tile 0 of every unit; per 32-row step, cycles from the previous barrier to "loads issued" (contains the gathered rows'
+addresses and every fourth pair of steps a stage of the gather table), "MFMAs issued", "LDS stores issued" (contains the wait for the step's data), "barrier passed"."""
 import ctypes
 import os
 import sys
