@@ -105,6 +105,7 @@ static int gemm_prepare(const m3_gemm_args *a, const char *who, GemmLaunch &L) {
   d.residual = a->residual; d.ld_res = a->ld_res;
   d.row_scale = a->row_scale; d.row_scale_div = a->row_scale ? a->row_scale_div : 1;
   d.row_scale_idx = a->row_scale ? a->row_scale_idx : nullptr;
+  d.row_scale_sh = div_shift(d.row_scale_div);
   d.act = a->act;
   d.M = a->M; d.N = a->N; d.K = a->K; d.G = a->G;
   d.group_offsets = a->group_offsets; d.tile_starts = a->tile_starts;
@@ -114,6 +115,8 @@ static int gemm_prepare(const m3_gemm_args *a, const char *who, GemmLaunch &L) {
   // 32-bit per-lane byte offsets: A rows (gathered source rows must be < M) and one B group must fit 4 GiB
   M3_REQUIRE((a->M + 1) * a->lda * es < ((int64_t)1 << 32) && (int64_t)a->N * a->ldb * es < ((int64_t)1 << 32),
              "%s: operand panel exceeds the 4 GiB reach of the 32-bit lane offsets", who);
+  // 32-bit rows in the kernels' prologues (row clamps, the row of the per-row factor)
+  M3_REQUIRE(a->M < ((int64_t)1 << 31), "%s: M %lld does not fit 32 bits", who, (long long)a->M);
 
   const GemmKernel kernel = L.kernel = choose_kernel(d, a->dtype);
   // the register-staged kernels have the run-time-flag epilogue only

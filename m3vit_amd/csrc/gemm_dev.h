@@ -24,6 +24,7 @@ struct GemmDev {
   const float *residual; int64_t ld_res;
   const float *row_scale; int32_t row_scale_div;   // value *= row_scale[srow / div] in front of the residual add,
   const int32_t *row_scale_idx;                    // srow = row_scale_idx ? row_scale_idx[m] : crow
+  int32_t row_scale_sh;                            // log2(row_scale_div) if a power of two, else -1 (as a_row_sh)
   int32_t act;
   int64_t M; int32_t N; int32_t K;
   int32_t G;
@@ -62,9 +63,10 @@ __device__ __forceinline__ TileOwner grouped_tile_rows(const int32_t *group_offs
   o.m_end = __builtin_amdgcn_readfirstlane(group_offsets[g + 1]);
   return o;
 }
-__device__ __forceinline__ TileOwner grouped_tile_owner(const int32_t *tile_starts, const int32_t *group_offsets, int G,
-                                                        int mt, int lane, int ts_lane) {
-  int g = 0, t0;
+// the group that owns row tile mt and the group's first row tile: no memory access with G <= 64 (ts_lane: grouped_live_tiles)
+__device__ __forceinline__ void grouped_tile_group(const int32_t *tile_starts, int G, int mt, int lane, int ts_lane, int &g,
+                                                   int &t0) {
+  g = 0;
   if (G <= 64) {
     // groups whose END prefix is <= mt lie wholly before the tile (the prefix is monotone; the last group never counts)
     g = __popcll(__ballot(lane < G - 1 && ts_lane <= mt));
@@ -73,6 +75,11 @@ __device__ __forceinline__ TileOwner grouped_tile_owner(const int32_t *tile_star
     while (g + 1 < G && tile_starts[g + 1] <= mt) ++g;
     t0 = tile_starts[g];
   }
+}
+__device__ __forceinline__ TileOwner grouped_tile_owner(const int32_t *tile_starts, const int32_t *group_offsets, int G,
+                                                        int mt, int lane, int ts_lane) {
+  int g, t0;
+  grouped_tile_group(tile_starts, G, mt, lane, ts_lane, g, t0);
   return grouped_tile_rows<128>(group_offsets, g, t0, mt);
 }
 
