@@ -231,7 +231,13 @@ int m3_ep_return(int handle, const void *send_rows, const int64_t *out_splits, v
  * bmm(gate_score, moe_outp), custom_moe_layer.py:298-305, is d moe_outp[t*k+j] = score[t,j] * d out[t], a row scaling
  * that commutes with the expert GEMM behind it, so the scaled copy [T*k, D] is never materialised ;
  * + residual[m,n] (fp32) if non-NULL ; store as c_dtype (M3_F32 or the act dtype).
- * Requirements: K*sizeof(elem) % 16 == 0, lda/ldb rows 16-byte aligned, N % 4 == 0. */
+ * Requirements: K*sizeof(elem) % 16 == 0, lda/ldb rows 16-byte aligned, N % 4 == 0.
+ * Reach: the kernels add a 32-bit byte offset per lane to the base of A and of a group's weight, so
+ * (M + 1) * lda * sizeof(elem) < 4 GiB, N * ldb * sizeof(elem) < 4 GiB (one group; the group stride N*ldb*g is 64-bit) and
+ * M < 2^31; a call outside any of these is refused (M3_ERR_ARG, m3_gemm_plan alike).  The A rule is measured with the M rows
+ * of the call: with a_row_idx every source row a_row_idx[m] / a_row_div must lie below M - nothing checks the indices, a
+ * larger one reads outside the offsets the rule covers.  C, pre_out, gelu_grad_pre and residual are addressed with 64 bits
+ * (destination row * leading dimension): no limit on ldc, ld_pre, ld_gpre, ld_res or on c_row_idx beyond the buffer itself. */
 typedef struct {
   const void *A; int64_t lda;
   const int32_t *a_row_idx; int32_t a_row_div;
@@ -292,7 +298,10 @@ int m3_gemm_plan(const m3_gemm_args *args, m3_gemm_plan_out *plan);
  * [splits][G][N][K]) then m3_wgrad_reduce sums them in order (beta = 1 accumulates
  * into dW, as the joint multi-task backward does: train/train_utils.py:449-457).
  * M < 2^31 rows and row strides (lddc, lda times the element size) below 4 GiB: the kernels form a row's byte offset as one
- * 32 x 32 -> 64-bit product; a call outside either is refused (m3_wgrad_multi alike). */
+ * 32 x 32 -> 64-bit product; a call outside either is refused (m3_wgrad_multi alike).  The LDS-DMA kernels and the streaming
+ * kernel form whole addresses in 32 bits and run only inside the 4 GiB reach, (M + 1) * lddc and (M + 1) * lda times the
+ * element size below 4 GiB (m3_wgrad_kernel: the step-downs).  That rule is measured with the M rows of the call: gathered
+ * rows c_row_idx[m] / c_row_div and a_row_idx[m] / a_row_div must lie below M for it to hold - nothing checks the indices. */
 /* A slab reduction that has not been launched yet (the arguments of m3_wgrad_reduce, or with chunk_rows > 0 of
  * m3_wgrad_reduce_grouped): the next m3_wgrad_tn call of the stream can carry it out in front of its own work
  * (m3_wgrad_args.prev), which saves one launch per weight-gradient GEMM. */
@@ -440,7 +449,9 @@ int m3_wgrad_skinny(int N, int K, int G);
 /* The kernel m3_wgrad_tn would launch for `args` under the current m3_wgrad_set_dma / m3_wgrad_set_big settings, after the
  * step-downs a call can force (a gather divisor that is no power of two, a per-row factor the family lacks for the dtype or
  * on rows that are not gathered, operands past the 4 GiB reach: 256 x 256 and the streaming kernel -> a 128 x 128 kernel,
- * LDS-DMA -> register-staged), and the template instance: gathered dC rows, gathered A rows, per-row factor.  Host code
+ * LDS-DMA -> register-staged), and the template instance: gathered dC rows, gathered A rows, per-row factor.  The reach is
+ * measured with M + 1 rows - (M + 1) * lddc * sizeof(elem) < 4 GiB and the same for lda: a row's offset plus a column offset
+ * stays below 2^32 - so gathered dC / A source rows must lie below M for the kernels inside it to stay inside.  Host code
  * shared with the launch (the same checks of the call and error codes), no GPU work, no operand pointer is read; the
  * descriptors behind args->prev are not looked at (they do not enter the choice; the launch checks them). */
 #define M3_WGRAD_KERNEL_STAGED 0   /* csrc/wgrad_staged.hip */

@@ -440,21 +440,26 @@ static void wgrad_prev_slices(WgradDev &d, dim3 &grid) {
 }
 
 // ------------------------------------------------------------------ the weight-gradient call
+// Every operand row within the 32-bit offsets a lane adds to the operand base.  M + 1 rows: a whole row past the last one, so
+// that row offset + column offset stays below 2^32; gathered source rows must be < M
+static bool wgrad_within_reach(const m3_wgrad_args *a, const WgradDev &d) {
+  return (a->M + 1) * d.lddc_b < ((int64_t)1 << 32) && (a->M + 1) * d.lda_b < ((int64_t)1 << 32);
+}
 // "The LDS-DMA form can run this call" (both wgrad_dma.hip kernels): power-of-two gather divisors (the kernels shift), every
-// operand row within the 32-bit offsets a lane adds to the operand base, and a per-row factor only on gathered rows of a
-// dtype whose instances multiply it in: fp16, and fp32 where the family has it (sc_f32: the 128 x 128 kernel)
+// operand row within reach, and a per-row factor only on gathered rows of a dtype whose instances multiply it in: fp16, and
+// fp32 where the family has it (sc_f32: the 128 x 128 kernel)
 static bool wgrad_dma_form(const m3_wgrad_args *a, const WgradDev &d, bool sc_f32) {
   const bool sc_ok = !a->c_row_scale || (a->c_row_idx && (a->dtype == M3_F16 || (sc_f32 && a->dtype == M3_F32)));
-  return sc_ok && d.a_row_sh >= 0 && d.c_row_sh >= 0 && (a->M + 1) * d.lddc_b < ((int64_t)1 << 32) &&
-         (a->M + 1) * d.lda_b < ((int64_t)1 << 32);
+  return sc_ok && d.a_row_sh >= 0 && d.c_row_sh >= 0 && wgrad_within_reach(a, d);
 }
 // A call the shape's kernel cannot run steps down: 256 x 256 tiles (the caller sized `splits` / `units` for that tile count;
 // any kernel works with them) and the streaming kernel (plain rows only: m3_wgrad_skinny reports the rule to the caller, who
 // sizes `splits` for it) to the 128 x 128 kernel m3_wgrad_set_dma's rule names, the LDS-DMA one of those to the register-staged
-// kernel, which takes everything
+// kernel, which takes everything.  The streaming kernel adds a 32-bit (row in the batch) x stride product, up to 60 rows, to a
+// batch's base: inside the 4 GiB reach a batch's rows are rows of the call and the product cannot wrap; past it, it can
 static WgradKernel wgrad_demote(WgradKernel kern, const m3_wgrad_args *a, const WgradDev &d) {
   const bool plain = !a->c_row_idx && !a->a_row_idx && !a->c_row_scale && !a->bias_ws && !a->chunk_rows && !a->direct_dW;
-  if ((kern == WGRAD_BIG && !wgrad_dma_form(a, d, false)) || (kern == WGRAD_SKINNY && !plain))
+  if ((kern == WGRAD_BIG && !wgrad_dma_form(a, d, false)) || (kern == WGRAD_SKINNY && !(plain && wgrad_within_reach(a, d))))
     kern = wgrad_tile128_kernel(a->N, a->K, a->G, a->dtype);
   if (kern == WGRAD_DMA && !wgrad_dma_form(a, d, true)) kern = WGRAD_STAGED;
   return kern;

@@ -9,7 +9,10 @@
 * assert_within(out, ref64, bound64) - the elementwise check |out - ref| <= bound, NaN counting as a failure.
 * the error-bound builders, one per kernel family (derivations next to each).
 * snapshot() / unchanged() - the inputs of a call keep their bits.
-* topk_agrees() - a kernel's top-k selection against an fp64 top-k, order free only inside the error bound.
+* far_rows(rows, cols, ld_bytes, dtype) / reach_stride(rows) - an operand whose rows lie megabytes apart inside one unfilled
+  allocation, so that its last rows start past 2 or 4 GiB from its base (tests/test_far_operands_gpu.py); check_outside()
+  proves that a far output wrote nothing between its rows.
+* topk_agrees() -a kernel's top-k selection against an fp64 top-k, order free only inside the error bound.
 """
 import math
 
@@ -106,6 +109,71 @@ def guarded_ws(n, dtype=torch.float32, device="cuda"):
         if i is not None:
             raise AssertionError(f"{what}: {cnt} element(s) outside the reported {n} changed; first at offset {i - g.start}")
     return view, check
+
+
+REACH = 1 << 32                  # bytes: what a 32-bit lane offset added to an operand base can address
+
+
+def reach_stride(rows, reach=REACH):
+    """the row stride (bytes) of the "just under the reach" cases: the largest multiple of 16 with (rows + 1) * ld < reach -
+    the rule of m3_gemm_nt's A panel and of the weight gradient's LDS-DMA forms.  For rows = 300: 14 268 992, so the rows
+    151 .. 299 start above 2^31"""
+    return (reach - 1) // (rows + 1) // 16 * 16
+
+
+class _Far:
+    """one byte allocation that operands with a huge row stride are windows of; nothing is filled (fill() does)"""
+
+    def __init__(self, rows, ld_bytes, row_bytes, device="cuda"):
+        assert ld_bytes % 16 == 0 and 0 < row_bytes <= ld_bytes
+        self.rows, self.ld_bytes = rows, ld_bytes
+        self.nbytes = -(-((rows - 1) * ld_bytes + row_bytes) // 16) * 16
+        self.buf = torch.empty(self.nbytes, dtype=torch.uint8, device=device)
+        assert self.buf.data_ptr() % 16 == 0
+
+    def view(self, cols, dtype, col_byte=0):
+        """the [rows, cols] window whose row r starts col_byte bytes into row r of the allocation"""
+        es = torch.empty(0, dtype=dtype).element_size()
+        assert col_byte % 16 == 0 and self.ld_bytes % es == 0
+        assert (self.rows - 1) * self.ld_bytes + col_byte + cols * es <= self.nbytes, "the window runs past the allocation"
+        flat = self.buf[: self.nbytes // es * es].view(dtype)
+        return torch.as_strided(flat, (self.rows, cols), (self.ld_bytes // es, 1), col_byte // es)
+
+    def fill(self, dtype):
+        """the sentinel of `dtype` over the whole allocation, in one fill_"""
+        it, v = _ival(dtype)
+        self.buf.view(it).fill_(v)
+
+    def check_outside(self, windows, dtype, what="far output", chunk_bytes=1 << 28):
+        """everything outside the windows [(col_byte, row bytes), ..] of every row still holds fill(dtype)'s sentinel.  Row
+        chunks of at most chunk_bytes, so that no temporary comes near 2 GiB"""
+        it, v = _ival(dtype)
+        ies = torch.empty(0, dtype=it).element_size()
+        ld = self.ld_bytes // ies
+        words = self.buf.view(it)
+        step = max(1, chunk_bytes // self.ld_bytes)
+        for r0 in range(0, self.rows, step):
+            r1 = min(r0 + step, self.rows)
+            part = words[r0 * ld: min(r1 * ld, words.numel())]
+            bad = part != v
+            for cb, nb in windows:
+                torch.as_strided(bad, (r1 - r0, nb // ies), (ld, 1), cb // ies).fill_(False)
+            if bool(bad.any()):
+                i = int(bad.nonzero()[0])
+                r, c = divmod(i, ld)
+                raise AssertionError(f"{what}: {int(bad.sum())} word(s) outside the written windows changed; first in row {r0 + r} "
+                                     f"at byte {c * ies} of the row (row stride {self.ld_bytes} bytes)")
+
+
+def far_rows(rows, cols, ld_bytes, dtype, col_byte=0, device="cuda"):
+    """(view [rows, cols] of `dtype` whose rows are ld_bytes apart, its allocation): one torch.empty of exactly
+    (rows - 1) * ld_bytes + col_byte + cols * es bytes rounded up to 16, of which view.copy_() touches the rows' own bytes
+    only - so an operand can reach past 2 and 4 GiB while a few hundred KB of it are ever written.  view.data_ptr() and
+    view.stride(0) are what the argument structs take; further operands of the same rows are allocation.view(cols, dtype,
+    col_byte) (make the first window the one that ends last)"""
+    es = torch.empty(0, dtype=dtype).element_size()
+    far = _Far(rows, ld_bytes, col_byte + cols * es, device)
+    return far.view(cols, dtype, col_byte), far
 
 
 def sentinel_like(t):

@@ -339,3 +339,46 @@ def test_relative_l2_alone_misses_gate_defects_the_contract_catches(gate_inputs)
     missed = [d for d in ("dense_past_T", "load_counts_selected") if run_gate(gate_inputs, d, k=GE - 1)[1]]
     missed += [d for d in ("act_truncated",) if run_gate_bwd(gate_inputs, d)[1]]
     assert "dense_past_T" in missed and "act_truncated" in missed, missed
+
+
+# ----------------------------------------------------------------------------------------------------- far operands
+def test_far_rows_places_row_r_at_r_times_the_stride():
+    """far_rows on a small stride (CPU, a few KB): the allocation is exactly the span of the rows rounded up to 16 bytes, row r
+    starts r * ld_bytes behind row 0, windows of the same rows share the allocation, copy_ touches the rows' own bytes only,
+    and check_outside finds a write that lands between two rows - as a store whose offset wrapped at 32 bits would"""
+    rows, cols, ld_b, cb = 7, 24, 400 * 16, 64
+    for dt in (torch.float16, torch.float32):
+        es = torch.empty(0, dtype=dt).element_size()
+        v, far = kc.far_rows(rows, cols, ld_b, dt, col_byte=cb, device=DEV)
+        assert far.buf.numel() == -(-((rows - 1) * ld_b + cb + cols * es) // 16) * 16
+        assert tuple(v.shape) == (rows, cols) and v.stride() == (ld_b // es, 1)
+        assert v.data_ptr() - far.buf.data_ptr() == cb and v.data_ptr() % 16 == 0
+        for r in range(rows):
+            assert v[r].data_ptr() - v.data_ptr() == r * ld_b
+        w = far.view(8, dt)                                          # a second window of the same rows, in front of the first
+        assert w.data_ptr() == far.buf.data_ptr() and w[rows - 1].data_ptr() - w.data_ptr() == (rows - 1) * ld_b
+        with pytest.raises(AssertionError, match="past the allocation"):
+            far.view(cols + 8, dt, col_byte=cb)
+        far.fill(dt)
+        assert kc.same_bits(v.contiguous(), kc.sentinel_like(v))
+        far.check_outside([], dt)
+        vals = torch.randn(rows, cols).to(dt)
+        v.copy_(vals)
+        assert kc.same_bits(v.contiguous(), vals)
+        far.check_outside([(cb, cols * es)], dt)                        # only the rows' own bytes changed
+        with pytest.raises(AssertionError, match="row 0"):
+            far.check_outside([(cb, (cols - 4) * es)], dt)              # the window's last columns count as outside
+        far.buf[3 * ld_b + cb + cols * es] = 0                          # one byte behind row 3
+        for chunk in (1 << 28, ld_b, 2 * ld_b):                         # whole, one row and two rows per chunk
+            with pytest.raises(AssertionError, match=rf"row 3 at byte {cb + cols * es}"):
+                far.check_outside([(cb, cols * es)], dt, chunk_bytes=chunk)
+
+
+def test_reach_stride_is_the_last_16_byte_step_under_the_reach():
+    assert kc.reach_stride(300) == 14_268_992
+    for rows in (1, 3, 100, 300, 333, 1000, 11000, 2 ** 20):
+        ld = kc.reach_stride(rows)
+        assert ld % 16 == 0 and (rows + 1) * ld < 2 ** 32 <= (rows + 1) * (ld + 16)
+    ld = kc.reach_stride(300)
+    assert 150 * ld < 2 ** 31 < 151 * ld and 299 * ld + 2 * 1024 < 2 ** 32       # rows 151 .. 299 start above 2^31
+    assert kc.reach_stride(9, reach=1 << 12) == 400
