@@ -18,7 +18,7 @@
 // Arithmetic order is pinned (and mirrored by oracle/gate_route.c) so that expert
 // indices are bit-exact: sequential fmaf chain over d starting from the bias, selection
 // on the noisy logits with ties -> lowest index.
-#include "common.h"
+#include "route_dev.h"
 
 #pragma clang fp contract(off)
 
@@ -341,44 +341,6 @@ struct BalanceDev {
   const int32_t *part_count; int32_t *blk_base; int32_t *counts; int32_t *offsets; int32_t *tile_starts; int64_t *counts64;
 };
 
-// one wave per expert (64 blocks per step, shuffle scan), then offsets / tile prefix by one thread
-__device__ __forceinline__ void route_scan_blocks(const BalanceDev &p) {
-  __shared__ int32_t tot[64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, E = p.E;
-  for (int e = wave; e < E; e += 1024 / 64) {
-    int32_t carry = 0;
-    for (int b0 = 0; b0 < p.nblk; b0 += 64) {
-      const int b = b0 + lane;
-      const int32_t v = b < p.nblk ? p.part_count[(int64_t)b * E + e] : 0;
-      int32_t inc = v;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int32_t up = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += up;
-      }
-      if (b < p.nblk) p.blk_base[(int64_t)b * E + e] = carry + inc - v;
-      carry += __shfl(inc, 63, 64);
-    }
-    if (lane == 0) {
-      tot[e] = carry;
-      p.counts[e] = carry;
-      if (p.counts64) p.counts64[e] = carry;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int32_t o = 0, ts = 0;
-    for (int i = 0; i < E; ++i) {
-      p.offsets[i] = o;
-      p.tile_starts[i] = ts;
-      o += tot[i];
-      ts += (tot[i] + 127) / 128;
-    }
-    p.offsets[E] = o;
-    p.tile_starts[E] = ts;
-  }
-}
-
 __device__ __forceinline__ void cv2_and_grad(const float *v, int E, float &cv, float *grad_scratch) {
   // unbiased var / (mean^2 + 1e-10); zero for a single expert
   float mean = 0.f;
@@ -394,7 +356,10 @@ __device__ __forceinline__ void cv2_and_grad(const float *v, int E, float &cv, f
 }
 
 __global__ __launch_bounds__(1024) void balance_kernel(const BalanceDev p) {
-  if (blockIdx.x == 1) { route_scan_blocks(p); return; }
+  if (blockIdx.x == 1) {                             // E <= 64 here
+    route_scan<1024, 64>(p.part_count, p.nblk, p.E, p.blk_base, p.counts, p.offsets, p.tile_starts, p.counts64);
+    return;
+  }
   // thread (r, e): e = tid % E, r = tid / E sums rows r, r + RL, ... (4 independent loads in flight),
   // then the RL row-lanes are added in lane order by thread (0, e)
   __shared__ float s_imp[1024], s_prob[1024];

@@ -37,43 +37,13 @@ __device__ __forceinline__ int class_label(const void *__restrict__ lab, int i) 
   }
 }
 
-// a workgroup's four partials: wave sums, then the four waves in order
-__device__ __forceinline__ void block_partials(float s0, float s1, int c0, int c1, float *__restrict__ ws) {
-  __shared__ float sh_f[2][4];
-  __shared__ int sh_i[2][4];
-  const int t = threadIdx.x, nblk = gridDim.x;
-  s0 = wave_sum(s0); s1 = wave_sum(s1);
-  c0 = wave_sum_i(c0); c1 = wave_sum_i(c1);
-  if ((t & 63) == 0) { sh_f[0][t >> 6] = s0; sh_f[1][t >> 6] = s1; sh_i[0][t >> 6] = c0; sh_i[1][t >> 6] = c1; }
-  __syncthreads();
-  if (t == 0) {
-    const int b = blockIdx.x;
-    ws[b] = ((sh_f[0][0] + sh_f[0][1]) + sh_f[0][2]) + sh_f[0][3];
-    ws[nblk + b] = ((sh_f[1][0] + sh_f[1][1]) + sh_f[1][2]) + sh_f[1][3];
-    ((int32_t *)ws)[2 * nblk + b] = sh_i[0][0] + sh_i[0][1] + sh_i[0][2] + sh_i[0][3];
-    ((int32_t *)ws)[3 * nblk + b] = sh_i[1][0] + sh_i[1][1] + sh_i[1][2] + sh_i[1][3];
-  }
-}
-
 // -------------------------------------------------------------------------------------------------------- finalize
 __global__ __launch_bounds__(256) void loss_finalize_kernel(const float *__restrict__ ws, int nblk, int kind, double numel,
                                                             int has_pw, double pos_weight, int32_t *__restrict__ rec) {
-  __shared__ double sh_s[2][256];
-  __shared__ long long sh_c[2][256];
-  const int t = threadIdx.x;
-  double s0 = 0.0, s1 = 0.0;
-  long long c0 = 0, c1 = 0;
-  for (int i = t; i < nblk; i += 256) {              // thread t: blocks t, t + 256, ... in order
-    s0 += (double)ws[i];
-    s1 += (double)ws[nblk + i];
-    c0 += ((const int32_t *)ws)[2 * nblk + i];
-    c1 += ((const int32_t *)ws)[3 * nblk + i];
-  }
-  sh_s[0][t] = s0; sh_s[1][t] = s1; sh_c[0][t] = c0; sh_c[1][t] = c1;
-  __syncthreads();
-  if (t != 0) return;
-  s0 = s1 = 0.0; c0 = c1 = 0;
-  for (int i = 0; i < 256; ++i) { s0 += sh_s[0][i]; s1 += sh_s[1][i]; c0 += sh_c[0][i]; c1 += sh_c[1][i]; }
+  const Totals<2, 2> tot = reduce_partials<2, 2>(ws, nblk, nblk);
+  if (threadIdx.x != 0) return;
+  const double s0 = tot.s[0], s1 = tot.s[1];
+  const long long c0 = tot.c[0], c1 = tot.c[1];
   float loss, coef, coef2 = 0.f;
   int n0 = (int)c0, n1 = 0, bad = 0;
   if (kind == K_CE || kind == K_L1) {                // mean over the valid: 0 / 0 = NaN as the reference, and a zero gradient
@@ -93,13 +63,7 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float *__restr
     coef2 = (float)((1.0 - w) / numel);
     n1 = (int)n_neg;
   }
-  ((float *)rec)[M3_LOSS_REC_VALUE] = loss;
-  ((float *)rec)[M3_LOSS_REC_COEF] = coef;
-  ((float *)rec)[M3_LOSS_REC_COEF2] = coef2;
-  rec[M3_LOSS_REC_N_VALID] = n0;
-  rec[M3_LOSS_REC_N_AUX] = n1;
-  rec[M3_LOSS_REC_N_BAD] = bad;
-  rec[6] = rec[7] = 0;
+  write_loss_record(rec, loss, coef, coef2, n0, n1, bad);
 }
 
 // ------------------------------------------------------------------------------------------ cross-entropy, planar
@@ -160,7 +124,7 @@ __global__ __launch_bounds__(LS_THREADS) void ce_fwd_planar_kernel(const T *__re
     }
     if (on) Pack<float, V>::store(lse + pix, out);
   }
-  block_partials(acc, 0.f, nv, nb, ws);
+  block_partials<2, 2>({acc, 0.f}, {nv, nb}, ws);
 }
 
 template <typename T, int V, int L>
@@ -248,46 +212,15 @@ __global__ __launch_bounds__(LS_THREADS) void ce_fwd_cl1_kernel(const T *__restr
       else if (li != 255) ++nb;
     }
   }
-  block_partials(acc, 0.f, nv, nb, ws);
+  block_partials<2, 2>({acc, 0.f}, {nv, nb}, ws);
 }
 
 // The vector path of the same reduction (C a multiple of 4: lane j holds channels 4j .. 4j + 3, at most 64 lanes).  What paces
 // the shuffle form above is not memory: its shuffles are LDS round trips (ds_bpermute) in dependent chains inside run-time
-// loops - measured with 4 channels per lane at 8 x 40 x 480 x 640 fp32: 226 us, 1.7 TB/s, 0.29 of m3_add_f32's rate.  Here the first four levels of a group's reduction are DPP row operations (quad
-// permutes, then the half-row and row mirrors: full-rate VALU, every lane of the group ends with the same bits), only groups of
+// loops - measured with 4 channels per lane at 8 x 40 x 480 x 640 fp32: 226 us, 1.7 TB/s, 0.29 of m3_add_f32's rate.  Here the first four levels of a group's reduction are DPP row operations
+// (group_allreduce, reduce_dev.h), only groups of
 // 32 and 64 lanes fall back to a shuffle; x[label] is not reduced at all - the lane that holds the label's chunk adds the
 // pixel's term; every level runs over the U steps together; and the next pass's loads are issued before this one is reduced.
-template <int CTRL> __device__ __forceinline__ float dpp_f(float v) { return __int_as_float(dpp_i<CTRL>(__float_as_int(v))); }
-template <bool MAX> __device__ __forceinline__ float red2(float a, float b) { return MAX ? fmaxf(a, b) : a + b; }
-
-template <bool MAX, int U>
-__device__ __forceinline__ void group_allreduce(float (&v)[U], int gsh) {
-  if (gsh >= 1) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = red2<MAX>(v[u], dpp_f<0xB1>(v[u]));       // quad_perm [1,0,3,2]
-  }
-  if (gsh >= 2) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = red2<MAX>(v[u], dpp_f<0x4E>(v[u]));       // quad_perm [2,3,0,1]
-  }
-  if (gsh >= 3) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = red2<MAX>(v[u], dpp_f<0x141>(v[u]));      // row_half_mirror: the other quad of 8 lanes
-  }
-  if (gsh >= 4) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = red2<MAX>(v[u], dpp_f<0x140>(v[u]));      // row_mirror: the other half of 16 lanes
-  }
-  if (gsh >= 5) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = red2<MAX>(v[u], __shfl_xor(v[u], 16, 64));
-  }
-  if (gsh >= 6) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = red2<MAX>(v[u], __shfl_xor(v[u], 32, 64));
-  }
-}
-
 template <typename T, int L>
 __global__ __launch_bounds__(LS_THREADS) void ce_fwd_cl4_kernel(const T *__restrict__ x, const void *__restrict__ lab, int C,
                                                                 int npix, int gsh, float *__restrict__ lse, float *__restrict__ ws) {
@@ -325,11 +258,11 @@ __global__ __launch_bounds__(LS_THREADS) void ce_fwd_cl4_kernel(const T *__restr
     float m[U], s[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) m[u] = in ? fmaxf(fmaxf(v[u][0], v[u][1]), fmaxf(v[u][2], v[u][3])) : -INFINITY;
-    group_allreduce<true, U>(m, gsh);
+    group_allreduce<OpMax>(m, gsh);
 #pragma unroll
     for (int u = 0; u < U; ++u)
       s[u] = in ? (__expf(v[u][0] - m[u]) + __expf(v[u][1] - m[u])) + (__expf(v[u][2] - m[u]) + __expf(v[u][3] - m[u])) : 0.f;
-    group_allreduce<false, U>(s, gsh);
+    group_allreduce<OpSum>(s, gsh);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const float out = m[u] + __logf(s[u]);
@@ -349,7 +282,7 @@ __global__ __launch_bounds__(LS_THREADS) void ce_fwd_cl4_kernel(const T *__restr
       li[u] = lin[u]; pc[u] = pcn[u]; on[u] = onn[u];
     }
   }
-  block_partials(acc, 0.f, nv, nb, ws);
+  block_partials<2, 2>({acc, 0.f}, {nv, nb}, ws);
 }
 
 // one pass over the flat [npix * C] span, V elements (of one pixel: V divides C) per access, two pieces per thread
@@ -440,7 +373,7 @@ __global__ __launch_bounds__(LS_THREADS) void flat_kernel(const T *__restrict__ 
       if (BWD && on[k]) Pack<T, V>::store(dx + (int64_t)uc[k] * V, d);
     }
   }
-  if (!BWD) block_partials(s0, s1, n0, 0, ws);
+  if (!BWD) block_partials<2, 2>({s0, s1}, {n0, 0}, ws);
 }
 
 // ------------------------------------------------------------------------------------------------------- normals
@@ -499,7 +432,7 @@ __global__ __launch_bounds__(LS_THREADS) void normals_kernel(const T *__restrict
       }
     }
   }
-  if (!BWD) block_partials(acc, 0.f, nv, 0, ws);
+  if (!BWD) block_partials<2, 2>({acc, 0.f}, {nv, 0}, ws);
 }
 
 static int finalize(const float *ws, int nblk, int kind, double numel, int has_pw, double pw, void *rec, hipStream_t s,

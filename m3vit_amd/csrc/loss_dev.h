@@ -1,8 +1,8 @@
 // What the kernels that read a dense prediction [B,C,H,W] next to its label share: the criterion (loss.hip) and the task
 // metrics (meter.hip).  Grid sizing, the shape and alignment checks of an entry point, the label-dtype dispatch and the lane
-// geometry of a channels-last pixel.
+// geometry of a channels-last pixel, the loss record.  The fixed-order sums all of them end in are reduce_dev.h's.
 #pragma once
-#include "common.h"
+#include "reduce_dev.h"
 #include <math.h>
 
 namespace m3 {
@@ -10,14 +10,17 @@ namespace m3 {
 constexpr int LS_THREADS = 256;
 constexpr int LS_MAX_BLOCKS = M3_LOSS_MAX_BLOCKS;   // 4 workgroups per CU; with two pieces per thread the bytes in flight of 8 per CU
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+// the eight words of a loss record (M3_LOSS_REC_*, include/m3vit_hip.h); words 6 and 7 are reserved and written as zero
+__device__ __forceinline__ void write_loss_record(int32_t *__restrict__ rec, float value, float coef, float coef2, int n_valid,
+                                                  int n_aux, int n_bad) {
+  ((float *)rec)[M3_LOSS_REC_VALUE] = value;
+  ((float *)rec)[M3_LOSS_REC_COEF] = coef;
+  ((float *)rec)[M3_LOSS_REC_COEF2] = coef2;
+  rec[M3_LOSS_REC_N_VALID] = n_valid;
+  rec[M3_LOSS_REC_N_AUX] = n_aux;
+  rec[M3_LOSS_REC_N_BAD] = n_bad;
+  rec[6] = rec[7] = 0;
 }
-
-// one DPP row operation (quad permutes, row mirrors): full-rate VALU, no LDS round trip
-template <int CTRL> __device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, false); }
 
 static inline int blocks_for(int64_t units, int per_block) {
   const int64_t b = (units + per_block - 1) / per_block;

@@ -107,37 +107,7 @@ __global__ __launch_bounds__(LS_THREADS) void iou_planar_kernel(const T *__restr
 }
 
 // channels-last: G = 2^gsh lanes read one pixel (loss.hip's geometry).  The group's argmax is two integer reductions - the
-// maximum of the keys, then the minimum of the channels that hold it - whose first four levels are DPP row operations.
-template <bool MAX> __device__ __forceinline__ uint32_t red2u(uint32_t a, uint32_t b) { return MAX ? (a > b ? a : b) : (a < b ? a : b); }
-
-template <bool MAX, int U>
-__device__ __forceinline__ void group_allreduce_u(uint32_t (&v)[U], int gsh) {
-  if (gsh >= 1) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = red2u<MAX>(v[u], (uint32_t)dpp_i<0xB1>((int)v[u]));      // quad_perm [1,0,3,2]
-  }
-  if (gsh >= 2) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = red2u<MAX>(v[u], (uint32_t)dpp_i<0x4E>((int)v[u]));      // quad_perm [2,3,0,1]
-  }
-  if (gsh >= 3) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = red2u<MAX>(v[u], (uint32_t)dpp_i<0x141>((int)v[u]));     // row_half_mirror
-  }
-  if (gsh >= 4) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = red2u<MAX>(v[u], (uint32_t)dpp_i<0x140>((int)v[u]));     // row_mirror
-  }
-  if (gsh >= 5) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = red2u<MAX>(v[u], (uint32_t)__shfl_xor((int)v[u], 16, 64));
-  }
-  if (gsh >= 6) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = red2u<MAX>(v[u], (uint32_t)__shfl_xor((int)v[u], 32, 64));
-  }
-}
-
+// maximum of the keys, then the minimum of the channels that hold it (group_allreduce, reduce_dev.h).
 constexpr uint32_t NO_CHANNEL = 0xFFFFu;
 
 // the scalar path (any C, any alignment): lane j of the group holds channels j, j + G, j + 2G, j + 3G (C <= 255 <= 4 * 64)
@@ -165,13 +135,13 @@ __global__ __launch_bounds__(LS_THREADS) void iou_cl1_kernel(const T *__restrict
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       key[r] = j + r * G < C ? max_key(v[r]) : 0u;
-      km[0] = red2u<true>(km[0], key[r]);
+      km[0] = OpMax::of(km[0], key[r]);
     }
-    group_allreduce_u<true, 1>(km, gsh);
+    group_allreduce<OpMax>(km, gsh);
 #pragma unroll
     for (int r = R - 1; r >= 0; --r)                                   // downwards: the lowest channel that holds the maximum stays
       if (key[r] == km[0]) cand[0] = (uint32_t)(j + r * G);
-    group_allreduce_u<false, 1>(cand, gsh);
+    group_allreduce<OpMin>(cand, gsh);
     if (j == 0 && on) iou_count(hist, (int)cand[0], li);
   }
   iou_flush(hist, ncls, ws);
@@ -218,9 +188,9 @@ __global__ __launch_bounds__(LS_THREADS) void iou_cl4_kernel(const T *__restrict
     for (int u = 0; u < U; ++u) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) key[u][k] = in ? max_key(v[u][k]) : 0u;
-      km[u] = red2u<true>(red2u<true>(key[u][0], key[u][1]), red2u<true>(key[u][2], key[u][3]));
+      km[u] = OpMax::of(OpMax::of(key[u][0], key[u][1]), OpMax::of(key[u][2], key[u][3]));
     }
-    group_allreduce_u<true, U>(km, gsh);
+    group_allreduce<OpMax>(km, gsh);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       cand[u] = NO_CHANNEL;
@@ -228,7 +198,7 @@ __global__ __launch_bounds__(LS_THREADS) void iou_cl4_kernel(const T *__restrict
       for (int k = 3; k >= 0; --k)
         if (in && key[u][k] == km[u]) cand[u] = (uint32_t)(j * 4 + k);
     }
-    group_allreduce_u<false, U>(cand, gsh);
+    group_allreduce<OpMin>(cand, gsh);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       if (j == 0 && on[u]) iou_count(hist, (int)cand[u], li[u]);
@@ -262,59 +232,17 @@ __global__ __launch_bounds__(1024) void iou_finalize_kernel(const int32_t *__res
 }
 
 // ------------------------------------------------------------------------------------- fp32 sums and counts of a workgroup
-// NF sums and NI counts per thread -> rows [NF + NI][nblk] of the workspace: wave sums, then the four waves in order
-template <int NF, int NI>
-__device__ __forceinline__ void sum_partials(const float (&s)[NF], const int (&c)[NI], float *__restrict__ ws) {
-  __shared__ float sh_f[NF][4];
-  __shared__ int sh_i[NI][4];
-  const int t = threadIdx.x, nblk = gridDim.x, b = blockIdx.x;
-#pragma unroll
-  for (int k = 0; k < NF; ++k) {
-    const float w = wave_sum(s[k]);
-    if ((t & 63) == 0) sh_f[k][t >> 6] = w;
-  }
-#pragma unroll
-  for (int k = 0; k < NI; ++k) {
-    const int w = wave_sum_i(c[k]);
-    if ((t & 63) == 0) sh_i[k][t >> 6] = w;
-  }
-  __syncthreads();
-  if (t < NF) ws[t * nblk + b] = ((sh_f[t][0] + sh_f[t][1]) + sh_f[t][2]) + sh_f[t][3];
-  else if (t < NF + NI) ((int32_t *)ws)[t * nblk + b] = sh_i[t - NF][0] + sh_i[t - NF][1] + sh_i[t - NF][2] + sh_i[t - NF][3];
-}
-
 // state[k] += the sum of row k over the blocks, in block order: double for the NF sums (words 0 .. NF - 1), int64 for the counts
 template <int NF, int NI>
 __global__ __launch_bounds__(256) void sums_finalize_kernel(const float *__restrict__ ws, int nblk, int64_t *__restrict__ state) {
-  __shared__ double sh_s[NF][256];
-  __shared__ long long sh_c[NI][256];
+  const Totals<NF, NI> tot = reduce_partials<NF, NI>(ws, nblk, nblk);
   const int t = threadIdx.x;
-  double s[NF];
-  long long c[NI];
 #pragma unroll
-  for (int k = 0; k < NF; ++k) s[k] = 0.0;
+  for (int k = 0; k < NF; ++k)
+    if (t == k) ((double *)state)[k] += tot.s[k];
 #pragma unroll
-  for (int k = 0; k < NI; ++k) c[k] = 0;
-  for (int i = t; i < nblk; i += 256) {                          // thread t: blocks t, t + 256, ... in order
-#pragma unroll
-    for (int k = 0; k < NF; ++k) s[k] += (double)ws[k * nblk + i];
-#pragma unroll
-    for (int k = 0; k < NI; ++k) c[k] += ((const int32_t *)ws)[(NF + k) * nblk + i];
-  }
-#pragma unroll
-  for (int k = 0; k < NF; ++k) sh_s[k][t] = s[k];
-#pragma unroll
-  for (int k = 0; k < NI; ++k) sh_c[k][t] = c[k];
-  __syncthreads();
-  if (t < NF) {
-    double a = 0.0;
-    for (int i = 0; i < 256; ++i) a += sh_s[t][i];
-    ((double *)state)[t] += a;
-  } else if (t < NF + NI) {
-    long long a = 0;
-    for (int i = 0; i < 256; ++i) a += sh_c[t - NF][i];
-    state[t] += a;
-  }
+  for (int k = 0; k < NI; ++k)
+    if (t == NF + k) state[NF + k] += tot.c[k];
 }
 
 // ---------------------------------------------------------------------------------------------------------------- depth
@@ -351,7 +279,7 @@ __global__ __launch_bounds__(LS_THREADS) void depth_kernel(const T *__restrict__
       }
     }
   }
-  sum_partials<2, 1>(s, n, ws);
+  block_partials<2, 1>(s, n, ws);
 }
 
 // -------------------------------------------------------------------------------------------------------------- normals
@@ -394,7 +322,7 @@ __global__ __launch_bounds__(LS_THREADS) void normals_meter_kernel(const T *__re
       ++n[3];
     }
   }
-  sum_partials<2, 4>(s, n, ws);
+  block_partials<2, 4>(s, n, ws);
 }
 
 // ------------------------------------------------------------------------------------------------------------- saliency

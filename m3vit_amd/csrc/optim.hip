@@ -3,7 +3,7 @@
 // m3_optim_step: one pass over p, g, m, v).  One workgroup per 4096-element chunk of one tensor, found by a binary search over
 // the device-resident descriptor table (as m3_cast_batch).  No atomics; every sum has a fixed order, so results are the same
 // bits from run to run.
-#include "common.h"
+#include "reduce_dev.h"
 #include <math.h>
 
 namespace m3 {
@@ -50,7 +50,6 @@ __device__ __forceinline__ uint32_t non_finite(float v) { return (__float_as_uin
 // ------------------------------------------------------------------------------------------------ norm partials
 __global__ __launch_bounds__(256) void optim_norm_kernel(const OptimDesc *__restrict__ descs, int n_desc, int total_chunks,
                                                          float *__restrict__ partials) {
-  __shared__ float s_sum[4];
   __shared__ uint32_t s_bad[4];
   const int b = blockIdx.x, t = threadIdx.x;
   const OptimDesc d = find_desc(descs, n_desc, b);
@@ -95,14 +94,10 @@ __global__ __launch_bounds__(256) void optim_norm_kernel(const OptimDesc *__rest
       }
     }
   }
-  acc = wave_sum(acc);
   bad = __any((int)bad) ? 1u : 0u;
-  if ((t & 63) == 0) { s_sum[t >> 6] = acc; s_bad[t >> 6] = bad; }
-  __syncthreads();
-  if (t == 0) {
-    partials[b] = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
-    partials[total_chunks + b] = (s_bad[0] | s_bad[1] | s_bad[2] | s_bad[3]) ? 1.f : 0.f;
-  }
+  if ((t & 63) == 0) s_bad[t >> 6] = bad;
+  block_partials<1>({acc}, partials);              // row 0 of [2][total_chunks]; its barrier also stands between s_bad's writes and reads
+  if (t == 0) partials[total_chunks + b] = (s_bad[0] | s_bad[1] | s_bad[2] | s_bad[3]) ? 1.f : 0.f;
 }
 
 // ----------------------------------------------------------------------------------------------------- finalize
@@ -112,23 +107,13 @@ __global__ __launch_bounds__(256) void optim_finalize_kernel(const float *__rest
                                                              const float *__restrict__ grad_scale,
                                                              const float *__restrict__ found_inf_in, float max_norm,
                                                              float *__restrict__ state) {
-  __shared__ double s_sum[256];
-  __shared__ int s_bad[256];
   __shared__ int s_skip, s_step;
   const int t = threadIdx.x;
-  double acc = 0.0;
-  int bad = 0;
-  for (int i = t; i < n_part; i += 256) {          // thread t: chunks t, t + 256, ... in order
-    acc += (double)partials[i];
-    bad |= partials[n_part + i] != 0.f;
-  }
-  s_sum[t] = acc;
-  s_bad[t] = bad;
-  __syncthreads();
+  // both rows as sums: the flags are 1.f or 0.f, so their sum (exact in double) is non-zero where their or is
+  const Totals<2, 0> tot = reduce_partials<2, 0>(partials, n_part, n_part);
   if (t == 0) {
-    double sum = 0.0;
-    int any = 0;
-    for (int i = 0; i < 256; ++i) { sum += s_sum[i]; any |= s_bad[i]; }
+    const double sum = tot.s[0];
+    int any = tot.s[1] != 0.0;
     OptimState *st = (OptimState *)state;
     const float inv_scale = grad_scale ? 1.0f / *grad_scale : 1.0f;
     if (found_inf_in && *found_inf_in != 0.f) any = 1;

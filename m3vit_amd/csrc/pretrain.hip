@@ -11,31 +11,6 @@ namespace m3 {
 
 constexpr int PT_THREADS = 256;
 
-// ---------------------------------------------------------------------------------------------- workgroup reductions
-// every thread returns the same bits: the xor butterfly of a wave is symmetric, the four wave results are added in order.
-// sh: 4 words of LDS; the leading barrier lets a caller reuse it for the next reduction.
-__device__ __forceinline__ float block_sum_f(float v, float *sh) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-__device__ __forceinline__ float block_max_f(float v, float *sh) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
-__device__ __forceinline__ int block_sum_i(int v, float *sh) {
-  v = wave_sum_i(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) ((int *)sh)[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((int *)sh)[0] + ((int *)sh)[1] + ((int *)sh)[2] + ((int *)sh)[3];
-}
-
 // ------------------------------------------------------------------------------------------------------ mix_batch
 // one element of sample `self` whose partner is `other`: inside a non-empty box the partner's pixel, outside it the own one
 // (both bit copies); with an empty box the Mixup blend - lam 1 and lam 0 are bit copies too (a -0 survives, a partner's Inf
@@ -141,12 +116,12 @@ __device__ __forceinline__ RowStats row_pass(const T *__restrict__ xr, const flo
       }
     }
   }
-  const float M = block_max_f(m, sh);
+  const float M = block_max(m, sh);
   s = m == -INFINITY ? 0.f : s * __expf(m - M);                       // a thread without a unit (C < 256 V) adds nothing
   RowStats r;
-  r.lse = M + __logf(block_sum_f(s, sh));
-  r.s0 = block_sum_f(a0, sh);
-  r.s1 = DENSE ? block_sum_f(a1, sh) : 1.f;
+  r.lse = M + __logf(block_sum(s, sh));
+  r.s0 = block_sum(a0, sh);
+  r.s1 = DENSE ? block_sum(a1, sh) : 1.f;
   return r;
 }
 
@@ -180,26 +155,11 @@ __global__ __launch_bounds__(PT_THREADS) void softce_fwd_kernel(const T *__restr
   }
 }
 
-// one workgroup: the B row losses in row order in double (thread t: rows t, t + 256, ...; then the 256 in order)
+// one workgroup: the B row losses and bad-label flags in row order (reduce_partials, reduce_dev.h)
 __global__ __launch_bounds__(256) void softce_finalize_kernel(const float *__restrict__ ws, int B, int32_t *__restrict__ rec) {
-  __shared__ double sh_s[256];
-  __shared__ int sh_c[256];
-  const int t = threadIdx.x;
-  double s = 0.0;
-  int c = 0;
-  for (int i = t; i < B; i += 256) { s += (double)ws[i]; c += ((const int32_t *)ws)[B + i]; }
-  sh_s[t] = s; sh_c[t] = c;
-  __syncthreads();
-  if (t != 0) return;
-  s = 0.0; c = 0;
-  for (int i = 0; i < 256; ++i) { s += sh_s[i]; c += sh_c[i]; }
-  ((float *)rec)[M3_LOSS_REC_VALUE] = (float)(s / (double)B);
-  ((float *)rec)[M3_LOSS_REC_COEF] = (float)(1.0 / (double)B);
-  ((float *)rec)[M3_LOSS_REC_COEF2] = 0.f;
-  rec[M3_LOSS_REC_N_VALID] = B;
-  rec[M3_LOSS_REC_N_AUX] = 0;
-  rec[M3_LOSS_REC_N_BAD] = c;
-  rec[6] = rec[7] = 0;
+  const Totals<1, 1> tot = reduce_partials<1, 1>(ws, B, B);
+  if (threadIdx.x != 0) return;
+  write_loss_record(rec, (float)(tot.s[0] / (double)B), (float)(1.0 / (double)B), 0.f, B, 0, (int)tot.c[0]);
 }
 
 // d x = (softmax(x) S - t) * coef * upstream over the flat [B * C] span, V elements of one row per access (V divides C)
@@ -265,9 +225,9 @@ __device__ __forceinline__ float row_lse_scaled(const T *__restrict__ xr, int C,
       m = mn;
     }
   }
-  const float M = block_max_f(m, sh);
+  const float M = block_max(m, sh);
   s = m == -INFINITY ? 0.f : s * __expf(m - M);
-  return M + __logf(block_sum_f(s, sh));
+  return M + __logf(block_sum(s, sh));
 }
 
 // the larger value wins, of equal values the lower index (m3_cls_eval_update's rule)
@@ -337,7 +297,7 @@ __global__ __launch_bounds__(PT_THREADS) void distill_fwd_kernel(const TX *__res
           }
         }
       }
-      const float dot = block_sum_f(a, sh);
+      const float dot = block_sum(a, sh);
       if (threadIdx.x == 0) {
         lse[row] = lx;
         ((float *)aux)[row] = lt;
@@ -357,22 +317,9 @@ __global__ __launch_bounds__(PT_THREADS) void distill_fwd_kernel(const TX *__res
 // one workgroup: the B row terms in row order in double (as softce_finalize_kernel); value = sum * num / den
 __global__ __launch_bounds__(256) void distill_finalize_kernel(const float *__restrict__ ws, int B, double num, double den,
                                                                float coef, int32_t *__restrict__ rec) {
-  __shared__ double sh_s[256];
-  const int t = threadIdx.x;
-  double s = 0.0;
-  for (int i = t; i < B; i += 256) s += (double)ws[i];
-  sh_s[t] = s;
-  __syncthreads();
-  if (t != 0) return;
-  s = 0.0;
-  for (int i = 0; i < 256; ++i) s += sh_s[i];
-  ((float *)rec)[M3_LOSS_REC_VALUE] = (float)(s * num / den);
-  ((float *)rec)[M3_LOSS_REC_COEF] = coef;
-  ((float *)rec)[M3_LOSS_REC_COEF2] = 0.f;
-  rec[M3_LOSS_REC_N_VALID] = B;
-  rec[M3_LOSS_REC_N_AUX] = 0;
-  rec[M3_LOSS_REC_N_BAD] = 0;
-  rec[6] = rec[7] = 0;
+  const Totals<1, 0> tot = reduce_partials<1, 0>(ws, B, B);
+  if (threadIdx.x != 0) return;
+  write_loss_record(rec, (float)(tot.s[0] * num / den), coef, 0.f, B, 0, 0);
 }
 
 // d x over the flat [B * C] span, V elements of one row per access.  SOFT: (exp(x / tau - lse_x) - exp(t / tau - lse_t)) coef
@@ -441,23 +388,13 @@ __global__ __launch_bounds__(PT_THREADS) void cls_eval_rows_kernel(const T *__re
 
 // one workgroup ADDS the batch to state: f64 loss_sum, correct1, correct5, count, then i64 n_bad; rows in row order
 __global__ __launch_bounds__(256) void cls_eval_finalize_kernel(const float *__restrict__ ws, int B, double *__restrict__ state) {
-  __shared__ double sh_s[256];
-  __shared__ int sh_c[3][256];
-  const int t = threadIdx.x;
-  const int32_t *wi = (const int32_t *)ws;
-  double s = 0.0;
-  int c1 = 0, c5 = 0, nb = 0;
-  for (int i = t; i < B; i += 256) { s += (double)ws[i]; c1 += wi[B + i]; c5 += wi[2 * B + i]; nb += wi[3 * B + i]; }
-  sh_s[t] = s; sh_c[0][t] = c1; sh_c[1][t] = c5; sh_c[2][t] = nb;
-  __syncthreads();
-  if (t != 0) return;
-  s = 0.0; c1 = c5 = nb = 0;
-  for (int i = 0; i < 256; ++i) { s += sh_s[i]; c1 += sh_c[0][i]; c5 += sh_c[1][i]; nb += sh_c[2][i]; }
-  state[M3_CLS_EVAL_LOSS_SUM] += s;
-  state[M3_CLS_EVAL_CORRECT1] += (double)c1;
-  state[M3_CLS_EVAL_CORRECT5] += (double)c5;
+  const Totals<1, 3> tot = reduce_partials<1, 3>(ws, B, B);            // counts: top-1 hits, top-5 hits, bad labels
+  if (threadIdx.x != 0) return;
+  state[M3_CLS_EVAL_LOSS_SUM] += tot.s[0];
+  state[M3_CLS_EVAL_CORRECT1] += (double)tot.c[0];
+  state[M3_CLS_EVAL_CORRECT5] += (double)tot.c[1];
   state[M3_CLS_EVAL_COUNT] += (double)B;
-  ((int64_t *)state)[M3_CLS_EVAL_N_BAD] += nb;
+  ((int64_t *)state)[M3_CLS_EVAL_N_BAD] += tot.c[2];
 }
 
 // -------------------------------------------------------------------------------------------------------------- EMA

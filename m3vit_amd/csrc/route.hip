@@ -10,7 +10,7 @@
 //
 // Three tiny launches: block histograms -> one-block scan -> block-local stable ranks
 // (wave ballots; 64-wide).  Integer work, bit-exact against oracle/gate_route.c.
-#include "common.h"
+#include "route_dev.h"
 
 namespace m3 {
 
@@ -37,47 +37,13 @@ __global__ __launch_bounds__(RT_THREADS) void route_hist_kernel(const int32_t *i
   for (int e = threadIdx.x; e < E; e += RT_THREADS) blk_counts[(int64_t)blockIdx.x * E + e] = h[e];
 }
 
-// exclusive scan of the per-block histograms along the block axis, one WAVE per expert (64 blocks per
-// step, shuffle scan), then the expert offsets / tile prefix by one thread
+// one workgroup: the scan of route_dev.h
 constexpr int RT_SCAN_THREADS = 1024;
 __global__ __launch_bounds__(RT_SCAN_THREADS) void route_scan_kernel(const int32_t *blk_counts, int nblk, int E,
                                                                      int32_t *blk_base, int32_t *counts,
                                                                      int32_t *offsets, int32_t *tile_starts,
                                                                      int64_t *counts64) {
-  __shared__ int32_t tot[RT_MAX_E];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int e = wave; e < E; e += RT_SCAN_THREADS / 64) {
-    int32_t carry = 0;
-    for (int b0 = 0; b0 < nblk; b0 += 64) {
-      const int b = b0 + lane;
-      const int32_t v = b < nblk ? blk_counts[(int64_t)b * E + e] : 0;
-      int32_t inc = v;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int32_t up = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += up;
-      }
-      if (b < nblk) blk_base[(int64_t)b * E + e] = carry + inc - v;
-      carry += __shfl(inc, 63, 64);
-    }
-    if (lane == 0) {
-      tot[e] = carry;
-      counts[e] = carry;
-      if (counts64) counts64[e] = carry;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int32_t o = 0, ts = 0;
-    for (int i = 0; i < E; ++i) {
-      offsets[i] = o;
-      tile_starts[i] = ts;
-      o += tot[i];
-      ts += (tot[i] + 127) / 128;
-    }
-    offsets[E] = o;
-    tile_starts[E] = ts;
-  }
+  route_scan<RT_SCAN_THREADS, RT_MAX_E>(blk_counts, nblk, E, blk_base, counts, offsets, tile_starts, counts64);
 }
 
 // base_stride: prefix blocks per workgroup - 1 for m3_route_build's own histogram blocks (RT_BLOCK entries each), the

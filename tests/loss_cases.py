@@ -57,7 +57,10 @@ def multi_pass_cases():
                            thread, 1 048 576 (262 144) pixels a pass
       l1, bce (64,128,258) 2 113 536 elements: flat_kernel, two pieces of 4 (odd: 1) elements per thread, 2 097 152 (524 288) a pass
       normals (8,129,257)  265 224 pixels: normals_kernel, one pixel per thread, 262 144 a pass
-    These are larger than the 2 M elements of the other cases because a second pass cannot be had for less."""
+    These are larger than the 2 M elements of the other cases because a second pass cannot be had for less.
+    (All of them run the full 1024 workgroups.  The finalize launch, whose 256 threads add the workgroups' partials t, t + 256,
+    ..., has its ragged second round in cases(): ce C40 GRID_CAP, channels-last on aligned storage, is 7 680 steps of 4
+    pixels, 16 per workgroup: 480 workgroups.)"""
     return [("ce", 40, (2, 192, 176), None), ("ce", 2, (32, 128, 260), None), ("l1", 1, (64, 128, 258), None),
             ("bce", 1, (64, 128, 258), None), ("normals", 3, (8, 129, 257), 1), ("normals", 3, (8, 129, 257), 2)]
 

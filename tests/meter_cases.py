@@ -56,9 +56,15 @@ def multi_pass_cases():
                               prefetched pieces a pass hands to the next
       depth, edge (4,257,511) 525 308 elements: depth_kernel / flat_kernel, two pieces per thread: 524 288 a pass
       normals (8,129,257)     one pixel per thread: 262 144 a pass
-      sal (64,91,91)          8 281 pixels per image on 1024 / 64 = 16 workgroups of two pieces: 8 192 a pass"""
+      sal (64,91,91)          8 281 pixels per image on 1024 / 64 = 16 workgroups of two pieces: 8 192 a pass
+    One case is here for the finalize launch instead (sums_finalize_kernel: 256 threads add the workgroups' partials, thread t
+    those of workgroups t, t + 256, ...), which goes round more than once only above 256 workgroups and raggedly only off a
+    multiple of 256 - every case above runs the full 1024:
+      normals (3,159,161)     76 797 pixels, one per thread and 256 per workgroup: 300 workgroups, the last one partial, so
+                              a second round of 44 partials (the <2, 4> instance).  The <2, 1> instance has its own in
+                              depth (4,257,511) on aligned storage: 131 327 vectors of 4, 512 per workgroup, 257 workgroups."""
     return [("iou", 2, (8, 129, 257)), ("iou", 40, (2, 48, 48)), ("iou", 40, (2, 192, 176)), ("depth", 1, (4, 257, 511)),
-            ("edge", 1, (4, 257, 511)), ("normals", 3, (8, 129, 257)), ("sal", 1, (64, 91, 91))]
+            ("edge", 1, (4, 257, 511)), ("normals", 3, (8, 129, 257)), ("sal", 1, (64, 91, 91)), ("normals", 3, (3, 159, 161))]
 
 
 def case_id(c):

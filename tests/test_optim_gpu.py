@@ -2,7 +2,8 @@
 
 Inputs, references and bounds are tests/optim_cases.py's (tests/test_optim_cpu.py shows that torch's own fp32 optimizers keep
 the same bounds on the same inputs).  Every case uses the smallest shapes at which its mechanism can go wrong; all tensors
-of a case together stay under 1 M elements."""
+of a case together stay under 1 M elements - but optim_cases.MANY_CHUNKS_INPUTS, whose one 1.2 M-element tensor gives the
+norm's finalize launch more partials than it has threads."""
 import pytest
 import torch
 
@@ -175,21 +176,29 @@ def test_max_grad_norm_above_the_norm_changes_no_bit(ops):
     assert float(opt.last_grad_norm) < 1e6
 
 
+def _norm_within(opt, last_grads, what, n64=None):
+    """last_grad_norm after the last step, against the float64 norm n64 (default: of last_grads): sqrt of an fp32 sum of
+    squares (chunks of 4096 terms, then double): d sqrt(S) = dS / (2 sqrt S)"""
+    S = sum(float((g.double() ** 2).sum()) for g in last_grads)
+    n64 = S ** 0.5 if n64 is None else n64
+    assert abs(n64 - S ** 0.5) < 1e-9 * n64
+    bound = float(kc.sum_bound(torch.tensor(S), 4096, torch.tensor(S), F32)) / (2 * n64) + 2 * oc.U32 * n64
+    err = abs(float(opt.last_grad_norm) - n64)
+    print(f"{what}: last_grad_norm {float(opt.last_grad_norm)!r} float64 {n64!r} err / bound {err / bound:.3g}")
+    assert err <= bound
+
+
 def test_clip_matches_clip_grad_norm_then_step(ops):
     cls, group_kw, group_of, clip, _, lrs = oc.case("clip")
     params, grads = oc.inputs_of("clip")
     ref = oc.reference("clip")
     a, opt, _ = _optimizer_run(_fused_cls("adamw"), group_kw, group_of, params, grads, max_grad_norm=clip)
-    # last_grad_norm after the last step, against the float64 norm: sqrt of an fp32 sum of squares (chunks of 4096 terms,
-    # then double): d sqrt(S) = dS / (2 sqrt S)
-    S = sum(float((g.double() ** 2).sum()) for g in grads[-1])
-    n64 = float(ref[-1]["norm"])
-    assert abs(n64 - S ** 0.5) < 1e-9 * n64
-    bound = float(kc.sum_bound(torch.tensor(S), 4096, torch.tensor(S), F32)) / (2 * n64) + 2 * oc.U32 * n64
-    err = abs(float(opt.last_grad_norm) - n64)
-    print(f"last_grad_norm {float(opt.last_grad_norm)!r} float64 {n64!r} err / bound {err / bound:.3g}")
-    assert err <= bound
+    _norm_within(opt, grads[-1], "clip", float(ref[-1]["norm"]))
     oc.check_run(a, ref, grads, group_kw, group_of, cls, "clip", lrs=lrs, worst=WORST)
+    # the norm alone over 303 chunks: more partials than the finalize launch has threads (optim_cases.MANY_CHUNKS_INPUTS)
+    params, grads = oc.inputs(**oc.MANY_CHUNKS_INPUTS)
+    _, opt, _ = _optimizer_run(_fused_cls("adamw"), group_kw, [0] * len(params), params, grads, max_grad_norm=clip)
+    _norm_within(opt, grads[-1], "many chunks")
 
 
 def test_grad_scale_power_of_two_changes_no_bit(ops):
