@@ -1017,6 +1017,72 @@ typedef struct m3_augment_desc {
 int m3_augment_batch(const m3_augment_desc *descs, int n_maps, int B, int H, int W, int Ho, int Wo, int border,
                      const double *mats, const float *aux, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------- token sharing stage
+ * The persistent-sharing stage of a TokenBlock (models/moe/token/vision_transformer_moe.py:873-959): ShareabilityPredictor,
+ * transition_stage and apply_shared_broadcast as one row pass over the positions p in [0, P = B*N) of T task tensors, its
+ * backward, the predictor alone, the masked mean of Aggregation / AggregationStage, and one small launch for the index
+ * compaction and the integer statistics.  No host read, no atomics; the same bits from run to run.
+ *
+ * Task tensors: T separate contiguous [P, D] allocations in the activation dtype, handed over as a table of device
+ * addresses (m3_share_rows, filled by the host); nothing is stacked or copied.  Limits, refused and never worked around:
+ * 2 <= T <= M3_SHARE_MAX_T (M3_ERR_UNSUPPORTED); D a multiple of 8 in [8, M3_SHARE_MAX_D] (M3_ERR_UNSUPPORTED: a lane owns
+ * the 8-element chunks lane and lane + 64 of a row); Dg >= 0, P < 2^31, 16-byte aligned tensors (M3_ERR_ARG).
+ *
+ * m3_share_stage_fwd, per position and task t:  logits = [x_t[p] | task_emb[t]] @ w_gate (+ noise[t][p], the caller's Gumbel
+ * draws; NULL = none), w_gate f32 [D + Dg][2] in the parameter's layout, task_emb f32 [T][Dg] (NULL with Dg = 0), noise f32
+ * [T][P][2];  soft = softmax(logits / tau)[1];  G = soft, or the one-hot's second entry when hard (soft is then written
+ * too: the backward's straight-through gradient needs it; soft may be NULL otherwise).  M_t = G_t >= gamma, cleared where
+ * fewer than two tasks agree; shared_bits[p] bit t = M_t;  W_t = G_t M_t / (sum_s G_s M_s + eps);  shared_x[p] = sum_t W_t
+ * x_t[p] into the DENSE [P][D] buffer (zero rows where bits == 0);  y_t[p] = M_t ? shared_x[p] : x_t[p] (the row's own
+ * bits).  g, soft: f32 [T][P].
+ * m3_share_stage_bwd: from d y_t (a NULL entry = zeros), d shared_x (dense, NULL = zeros) and d g (f32 [T][P], NULL =
+ * zeros) to d x_t, d w_gate [D + Dg][2] and d task_emb [T][Dg] (both overwritten).  ws: m3_share_bwd_ws_elems floats, no
+ * initialisation: one partial row per workgroup, added in a fixed order by a second launch.
+ * m3_share_predict_fwd / _bwd: the predictor of ONE tensor (task_emb f32 [Dg], noise f32 [P][2], g / soft / d_g f32 [P]),
+ * the stage's own code for logits and G.
+ * m3_share_aggregate_fwd: v = (bits of mask_bits[p] below T) where agg_needed[p] (one byte per position; NULL = everywhere);
+ * agg[p] = sum_{s in v} x_s[p] / (|v| + eps) (dense, optional, zero rows where v is empty);  y_t[p] = v_t ? agg[p] : x_t[p].
+ * m3_share_aggregate_bwd: d x_s = v_s (d agg + sum_{t in v} d y_t) / (|v| + eps) + (1 - v_s) d y_s.
+ * m3_share_compact (one workgroup, M3_SHARE_SCAN_WIDTH positions per step of its scan): shared_flat_idx i32 [P] = the flat
+ * indices with bits != 0, ascending, the tail -1 (NULL: not wanted); count i32 [1] (NULL: not wanted); stats i64
+ * [M3_SHARE_STAT_WORDS] at the M3_SHARE_STAT_* words: POSITIONS, TASKTOKENS (set bits), PARTIAL (positions shared by some
+ * but not all T tasks) of PARTIAL_TOTAL = P, FLIPS (positions whose bits differ from prev_shared_bits) of FLIP_TOTAL (P, or
+ * 0 without prev_shared_bits), and the sharing regulariser's S (= POSITIONS) and S_T + t (positions with bit t, t < T). */
+#define M3_SHARE_MAX_T 8
+#define M3_SHARE_MAX_D 1024
+#define M3_SHARE_MAX_BLOCKS 1024
+#define M3_SHARE_SCAN_WIDTH 1024
+#define M3_SHARE_STAT_POSITIONS 0
+#define M3_SHARE_STAT_TASKTOKENS 1
+#define M3_SHARE_STAT_PARTIAL 2
+#define M3_SHARE_STAT_PARTIAL_TOTAL 3
+#define M3_SHARE_STAT_FLIPS 4
+#define M3_SHARE_STAT_FLIP_TOTAL 5
+#define M3_SHARE_STAT_S 6
+#define M3_SHARE_STAT_S_T 8
+#define M3_SHARE_STAT_WORDS 16
+typedef struct m3_share_rows { void *p[M3_SHARE_MAX_T]; } m3_share_rows;
+int m3_share_num_blocks(int64_t P);
+int64_t m3_share_bwd_ws_elems(int64_t P, int T, int D, int Dg);
+int m3_share_stage_fwd(const m3_share_rows *x, int dtype, int T, int64_t P, int D, const float *w_gate,
+                       const float *task_emb, int Dg, const float *noise, float tau, int hard, float gamma, float eps,
+                       const m3_share_rows *y, void *shared_x, int64_t *shared_bits, float *g, float *soft, void *stream);
+int m3_share_stage_bwd(const m3_share_rows *x, int dtype, int T, int64_t P, int D, const float *w_gate,
+                       const float *task_emb, int Dg, float tau, float eps, const int64_t *shared_bits, const float *g,
+                       const float *soft, const void *shared_x, const m3_share_rows *dy, const void *d_shared_x,
+                       const float *d_g, const m3_share_rows *dx, float *ws, float *d_w_gate, float *d_task_emb, void *stream);
+int m3_share_predict_fwd(const void *x, int dtype, int64_t P, int D, const float *w_gate, const float *task_emb, int Dg,
+                         const float *noise, float tau, int hard, float *g, float *soft, void *stream);
+int m3_share_predict_bwd(const void *x, int dtype, int64_t P, int D, const float *w_gate, const float *task_emb, int Dg,
+                         float tau, const float *g, const float *soft, const float *d_g, void *dx, float *ws,
+                         float *d_w_gate, float *d_task_emb, void *stream);
+int m3_share_aggregate_fwd(const m3_share_rows *x, int dtype, int T, int64_t P, int D, const int64_t *mask_bits,
+                           const void *agg_needed, float eps, const m3_share_rows *y, void *agg, void *stream);
+int m3_share_aggregate_bwd(const m3_share_rows *dy, int dtype, int T, int64_t P, int D, const int64_t *mask_bits,
+                           const void *agg_needed, float eps, const void *d_agg, const m3_share_rows *dx, void *stream);
+int m3_share_compact(const int64_t *shared_bits, const int64_t *prev_shared_bits, int64_t P, int T, int32_t *shared_flat_idx,
+                     int32_t *count, int64_t *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

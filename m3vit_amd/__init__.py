@@ -26,15 +26,19 @@ _LOSS_NAMES = ("SoftMaxwithLoss", "BalancedCrossEntropyLoss", "DepthLoss", "Norm
                "get_loss")
 _METER_NAMES = ("PerformanceMeter", "SemsegMeter", "HumanPartsMeter", "DepthMeter", "NormalsMeter", "SaliencyMeter", "EdgeMeter",
                 "AverageMeter", "get_single_task_meter", "calculate_multi_task_performance", "get_output")
+_SHARING_NAMES = ("ShareabilityPredictor", "Aggregation", "AggregationStage", "SharingRegularizationLoss", "SharingStage")
 
 
 def __getattr__(name):
-    """the criterion modules of m3vit_amd.losses and the task meters of m3vit_amd.meters, importable from the package (loaded
-    on first use: they need torch)"""
+    """the criterion modules of m3vit_amd.losses, the task meters of m3vit_amd.meters and the token sharing stage of
+    m3vit_amd.sharing, importable from the package (loaded on first use: they need torch)"""
     if name in _LOSS_NAMES:
         from . import losses
         return getattr(losses, name)
     if name in _METER_NAMES:
         from . import meters
         return getattr(meters, name)
+    if name in _SHARING_NAMES:
+        from . import sharing
+        return getattr(sharing, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -94,7 +94,8 @@ globals().update({py: STRUCTS["m3_" + c] for py, c in {         # the Python nam
     "WgradProblem": "wgrad_problem", "WgradMultiShape": "wgrad_multi_shape", "WgradMultiPlan": "wgrad_multi_plan_out",
     "WgradMultiArgs": "wgrad_multi_args", "AttentionPlan": "attention_plan_out", "CastDesc": "cast_desc",
     "OptimDesc": "optim_desc", "GateFwdArgs": "gate_fwd_args", "GateBwdArgs": "gate_bwd_args",
-    "LnParamGrads": "ln_param_grads", "AugmentDesc": "augment_desc", "Conv3x3Plan": "conv3x3_plan_out"}.items()})
+    "LnParamGrads": "ln_param_grads", "AugmentDesc": "augment_desc", "Conv3x3Plan": "conv3x3_plan_out",
+    "ShareRows": "share_rows"}.items()})
 WGRAD_MULTI_MAX = CONSTANTS["M3_WGRAD_MULTI_MAX"]
 
 

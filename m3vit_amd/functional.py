@@ -472,3 +472,94 @@ class BalancedBCEFn(torch.autograd.Function):
     def backward(ctx, g, _g_record):
         p, lab, record = ctx.saved_tensors
         return ops.loss_bce_bwd(p, lab, record, _upstream(g)), None, None
+
+
+# ------------------------------------------------------------------------------------------------- token sharing stage
+# csrc/share.hip.  Task tensors stay separate allocations; a gradient that autograd does not have (an output nobody used)
+# reaches the kernel as a NULL entry, not as a tensor of zeros.
+
+def _grad_like(g, ref):
+    """an incoming gradient in the layout the kernel reads: ref's dtype, contiguous"""
+    return None if g is None else g.to(ref.dtype).contiguous()
+
+
+class ShareStageFn(torch.autograd.Function):
+    """predictor + transition_stage + apply_shared_broadcast of a TokenBlock as ONE node (token/vision_transformer_moe.py:
+    873-959): forward m3_share_stage_fwd, backward m3_share_stage_bwd.
+    apply(w_gate, task_emb [T, Dg] or None, noise [T, P, 2] or None, tau, hard, gamma, eps, *xs)
+      -> (*ys, shared_x [P, D], shared_bits int64 [P], g [T, P])"""
+
+    @staticmethod
+    def forward(ctx, w_gate, task_emb, noise, tau, hard, gamma, eps, *xs):
+        xs = [x.detach().contiguous() for x in xs]
+        w = w_gate.detach().contiguous()
+        emb = None if task_emb is None else task_emb.detach().to(torch.float32).contiguous()
+        ys, sx, bits, g, soft = ops.share_stage_fwd(xs, w, emb, None if noise is None else noise.detach(), tau, hard, gamma, eps)
+        ctx.save_for_backward(w, emb, bits, g, soft, sx, *xs)
+        ctx.tau, ctx.eps, ctx.shapes = tau, eps, [x.shape for x in xs]
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(bits)
+        return (*[y.view(s) for y, s in zip(ys, ctx.shapes)], sx, bits, g)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        w, emb, bits, g, soft, sx, *xs = ctx.saved_tensors
+        T = len(xs)
+        dys = [_grad_like(d, xs[0]) for d in grads[:T]]
+        d_sx, d_g = _grad_like(grads[T], sx), _grad_like(grads[T + 2], g)
+        dxs, dw, demb = ops.share_stage_bwd(xs, w, emb, ctx.tau, ctx.eps, bits, g, soft, sx, dys, d_sx, d_g)
+        return (dw, demb, None, None, None, None, None, *[d.view(s) for d, s in zip(dxs, ctx.shapes)])
+
+
+class SharePredictFn(torch.autograd.Function):
+    """ShareabilityPredictor.forward of one tensor (token/shareability.py:40-85): m3_share_predict_fwd / _bwd.
+    apply(x [.., D], w_gate, task_emb [Dg] or None, noise [P, 2] or None, logit_offset [P, 2] or None, tau, hard) -> g [P].
+    logit_offset: logits computed outside (a per-sample or per-position task embedding's share), added where the noise
+    is; its gradient is (-d l1, d l1)."""
+
+    @staticmethod
+    def forward(ctx, x, w_gate, task_emb, noise, logit_offset, tau, hard):
+        x = x.detach().contiguous()
+        w = w_gate.detach().contiguous()
+        emb = None if task_emb is None else task_emb.detach().to(torch.float32).contiguous()
+        add = None if noise is None else noise.detach().to(torch.float32)
+        if logit_offset is not None:
+            off = logit_offset.detach().to(torch.float32)
+            add = off if add is None else add.reshape(off.shape) + off
+        g, soft = ops.share_predict_fwd(x, w, emb, None if add is None else add.contiguous(), tau, hard)
+        ctx.save_for_backward(x, w, emb, g, soft)
+        ctx.tau, ctx.offset = tau, logit_offset is not None
+        return g
+
+    @staticmethod
+    def backward(ctx, d_g):
+        x, w, emb, g, soft = ctx.saved_tensors
+        d_g = d_g.to(torch.float32).contiguous()
+        dx, dw, demb = ops.share_predict_bwd(x, w, emb, ctx.tau, g, soft, d_g)
+        d_off = None
+        if ctx.offset:
+            y = g if soft is None else soft
+            dl1 = d_g * y * (1.0 - y) / ctx.tau
+            d_off = torch.stack((-dl1, dl1), dim=-1)
+        return dx, dw, demb, None, d_off, None, None
+
+
+class ShareAggregateFn(torch.autograd.Function):
+    """Aggregation + AggregationStage (token/shareability.py:88-121, models/moe/aggregation_stages.py):
+    apply(mask_bits int64 [P], agg_needed bool [P] or None, eps, *xs) -> (*ys, agg [P, D])"""
+
+    @staticmethod
+    def forward(ctx, mask_bits, agg_needed, eps, *xs):
+        xs = [x.detach().contiguous() for x in xs]
+        ys, agg = ops.share_aggregate_fwd(xs, mask_bits, agg_needed, eps)
+        ctx.save_for_backward(mask_bits, agg_needed)
+        ctx.eps, ctx.shapes = eps, [x.shape for x in xs]
+        return (*[y.view(s) for y, s in zip(ys, ctx.shapes)], agg)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        mask_bits, agg_needed = ctx.saved_tensors
+        T = len(ctx.shapes)
+        dys = [d.contiguous() for d in grads[:T]]
+        dxs = ops.share_aggregate_bwd(dys, mask_bits, agg_needed, ctx.eps, grads[T].contiguous())
+        return (None, None, None, *[d.view(s) for d, s in zip(dxs, ctx.shapes)])

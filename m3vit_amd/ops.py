@@ -1801,3 +1801,186 @@ def tokens_bwd2(dtok, B, np_, D, dpatch, dpos, dcls, ddist, beta=0):
         _act(dpatch, "dpatch", B * np_ * D)
     check(lib().m3_tokens_bwd2(_p(dtok), B, np_, D, _p(dpatch), dt_code(dpatch.dtype) if dpatch is not None else M3_F32,
                                _p(dpos), _p(dcls), _p(ddist), beta, _stream()), "m3_tokens_bwd2")
+
+
+# ----------------------------------------------------------------------------- token sharing stage (csrc/share.hip)
+SHARE_MAX_T, SHARE_MAX_D = _lib.M3_SHARE_MAX_T, _lib.M3_SHARE_MAX_D
+SHARE_STAT_WORDS = _lib.M3_SHARE_STAT_WORDS
+
+
+def _share_tasks(T, what, tmin=2):
+    if not tmin <= T <= SHARE_MAX_T:
+        raise _lib.M3Error(f"{what}: {T} task tensors; the sharing kernels take {tmin} to {SHARE_MAX_T} tasks")
+
+
+def _share_rows(ts, P, D, dtype, name, allow_none=False):
+    """the table of device addresses of T separate [P, D] task tensors (nothing is stacked or copied)"""
+    rows = _lib.ShareRows()
+    for t, x in enumerate(ts):
+        if x is None and allow_none:
+            continue
+        _req(x, dtype, f"{name}[{t}]", numel=P * D)
+        rows.p[t] = x.data_ptr()
+    return rows
+
+
+def _share_common(xs, w_gate, task_emb, what, tmin=2):
+    xs = list(xs)
+    _share_tasks(len(xs), what, tmin)
+    x0 = _act(xs[0], f"{what}: x[0]")
+    D = x0.shape[-1]
+    P = x0.numel() // D
+    if D % 8 or not 8 <= D <= SHARE_MAX_D:
+        raise _lib.M3Error(f"{what}: D={D} must be a multiple of 8 in [8, {SHARE_MAX_D}]")
+    Dg = 0 if task_emb is None else task_emb.shape[-1]
+    if w_gate is not None:
+        _req(w_gate, torch.float32, "w_gate", numel=(D + Dg) * 2)
+        if task_emb is not None:
+            _req(task_emb, torch.float32, "task_emb", numel=len(xs) * Dg)
+    return xs, P, D, Dg
+
+
+def share_bwd_ws_elems(P, T, D, Dg) -> int:
+    return int(lib().m3_share_bwd_ws_elems(P, T, D, Dg))
+
+
+def share_stage_fwd(xs, w_gate, task_emb, noise, tau, hard, gamma=0.5, eps=1e-6):
+    """m3_share_stage_fwd over T separate task tensors [.., D].  task_emb f32 [T, Dg] or None, noise f32 [T, P, 2] or None.
+    Returns (ys, shared_x [P, D], bits int64 [P], g f32 [T, P], soft f32 [T, P] or None (soft mode: g is the soft score))."""
+    xs, P, D, Dg = _share_common(xs, w_gate, task_emb, "share_stage_fwd")
+    T, dt, dev = len(xs), xs[0].dtype, xs[0].device
+    if noise is not None:
+        _req(noise, torch.float32, "noise", numel=T * P * 2)
+    xr = _share_rows(xs, P, D, dt, "x")
+    ys = [torch.empty_like(x) for x in xs]
+    yr = _share_rows(ys, P, D, dt, "y")
+    sx = torch.empty((P, D), dtype=dt, device=dev)
+    bits = torch.empty(P, dtype=torch.int64, device=dev)
+    g = torch.empty((T, P), dtype=torch.float32, device=dev)
+    soft = torch.empty((T, P), dtype=torch.float32, device=dev) if hard else None
+    check(lib().m3_share_stage_fwd(byref(xr), dt_code(dt), T, P, D, _p(w_gate), _p(task_emb), Dg, _p(noise), float(tau),
+                                   int(bool(hard)), float(gamma), float(eps), byref(yr), _p(sx), _p(bits), _p(g), _p(soft),
+                                   _stream()), "m3_share_stage_fwd")
+    return ys, sx, bits, g, soft
+
+
+def share_stage_bwd(xs, w_gate, task_emb, tau, eps, bits, g, soft, sx, dys, d_sx=None, d_g=None, ws=None):
+    """m3_share_stage_bwd: (d x_t list, d w_gate [D + Dg, 2], d task_emb [T, Dg] or None).  dys: a list whose None entries
+    count as zeros; d_sx dense [P, D] or None; d_g f32 [T, P] or None."""
+    xs, P, D, Dg = _share_common(xs, w_gate, task_emb, "share_stage_bwd")
+    T, dt, dev = len(xs), xs[0].dtype, xs[0].device
+    _req(bits, torch.int64, "shared_bits", numel=P); _req(g, torch.float32, "g", numel=T * P)
+    _req(sx, dt, "shared_x", numel=P * D)
+    if soft is not None:
+        _req(soft, torch.float32, "soft", numel=T * P)
+    if d_sx is not None:
+        _req(d_sx, dt, "d_shared_x", numel=P * D)
+    if d_g is not None:
+        _req(d_g, torch.float32, "d_g", numel=T * P)
+    xr = _share_rows(xs, P, D, dt, "x")
+    dyr = _share_rows(dys, P, D, dt, "dy", allow_none=True)
+    dxs = [torch.empty_like(x) for x in xs]
+    dxr = _share_rows(dxs, P, D, dt, "dx")
+    n_ws = share_bwd_ws_elems(P, T, D, Dg)
+    if ws is None:
+        ws = torch.empty(max(n_ws, 4), dtype=torch.float32, device=dev)
+    _req(ws, torch.float32, "ws", min_numel=n_ws)
+    dw = torch.empty((D + Dg, 2), dtype=torch.float32, device=dev)
+    demb = torch.empty((T, Dg), dtype=torch.float32, device=dev) if Dg else None
+    if P == 0:
+        dw.zero_()
+        if demb is not None:
+            demb.zero_()
+    check(lib().m3_share_stage_bwd(byref(xr), dt_code(dt), T, P, D, _p(w_gate), _p(task_emb), Dg, float(tau), float(eps),
+                                   _p(bits), _p(g), _p(soft), _p(sx), byref(dyr), _p(d_sx), _p(d_g), byref(dxr), _p(ws),
+                                   _p(dw), _p(demb), _stream()), "m3_share_stage_bwd")
+    return dxs, dw, demb
+
+
+def share_predict_fwd(x, w_gate, task_emb, noise, tau, hard):
+    """m3_share_predict_fwd: the predictor of one tensor [.., D].  task_emb f32 [Dg] or None, noise f32 [P, 2] or None.
+    Returns (g f32 [P], soft f32 [P] or None)."""
+    (x,), P, D, Dg = _share_common([x], None, task_emb, "share_predict_fwd", tmin=1)
+    _req(w_gate, torch.float32, "w_gate", numel=(D + Dg) * 2)
+    if task_emb is not None:
+        _req(task_emb, torch.float32, "task_emb", numel=Dg)
+    if noise is not None:
+        _req(noise, torch.float32, "noise", numel=P * 2)
+    g = torch.empty(P, dtype=torch.float32, device=x.device)
+    soft = torch.empty(P, dtype=torch.float32, device=x.device) if hard else None
+    check(lib().m3_share_predict_fwd(_p(x), dt_code(x.dtype), P, D, _p(w_gate), _p(task_emb), Dg, _p(noise), float(tau),
+                                     int(bool(hard)), _p(g), _p(soft), _stream()), "m3_share_predict_fwd")
+    return g, soft
+
+
+def share_predict_bwd(x, w_gate, task_emb, tau, g, soft, d_g, ws=None):
+    """m3_share_predict_bwd: (d x, d w_gate, d task_emb [Dg] or None)"""
+    (x,), P, D, Dg = _share_common([x], None, task_emb, "share_predict_bwd", tmin=1)
+    _req(w_gate, torch.float32, "w_gate", numel=(D + Dg) * 2)
+    _req(g, torch.float32, "g", numel=P); _req(d_g, torch.float32, "d_g", numel=P)
+    if soft is not None:
+        _req(soft, torch.float32, "soft", numel=P)
+    dx = torch.empty_like(x)
+    n_ws = share_bwd_ws_elems(P, 1, D, Dg)
+    if ws is None:
+        ws = torch.empty(max(n_ws, 4), dtype=torch.float32, device=x.device)
+    _req(ws, torch.float32, "ws", min_numel=n_ws)
+    dw = torch.empty((D + Dg, 2), dtype=torch.float32, device=x.device)
+    demb = torch.empty(Dg, dtype=torch.float32, device=x.device) if Dg else None
+    if P == 0:
+        dw.zero_()
+        if demb is not None:
+            demb.zero_()
+    check(lib().m3_share_predict_bwd(_p(x), dt_code(x.dtype), P, D, _p(w_gate), _p(task_emb), Dg, float(tau), _p(g), _p(soft),
+                                     _p(d_g), _p(dx), _p(ws), _p(dw), _p(demb), _stream()), "m3_share_predict_bwd")
+    return dx, dw, demb
+
+
+def share_aggregate_fwd(xs, mask_bits, agg_needed, eps=1e-6, want_agg=True):
+    """m3_share_aggregate_fwd: (ys, agg [P, D] or None).  mask_bits int64 [P] (bit t: task t's mask), agg_needed bool [P] or
+    None (= everywhere)."""
+    xs, P, D, _ = _share_common(xs, None, None, "share_aggregate_fwd")
+    T, dt, dev = len(xs), xs[0].dtype, xs[0].device
+    _req(mask_bits, torch.int64, "mask_bits", numel=P)
+    if agg_needed is not None:
+        _req(agg_needed, torch.bool, "agg_needed", numel=P)
+    xr = _share_rows(xs, P, D, dt, "x")
+    ys = [torch.empty_like(x) for x in xs]
+    yr = _share_rows(ys, P, D, dt, "y")
+    agg = torch.empty((P, D), dtype=dt, device=dev) if want_agg else None
+    check(lib().m3_share_aggregate_fwd(byref(xr), dt_code(dt), T, P, D, _p(mask_bits), _p(agg_needed), float(eps), byref(yr),
+                                       _p(agg), _stream()), "m3_share_aggregate_fwd")
+    return ys, agg
+
+
+def share_aggregate_bwd(dys, mask_bits, agg_needed, eps=1e-6, d_agg=None):
+    """m3_share_aggregate_bwd: the d x_t list from the d y_t list (all given) and d agg (dense or None)"""
+    dys, P, D, _ = _share_common(dys, None, None, "share_aggregate_bwd")
+    T, dt = len(dys), dys[0].dtype
+    _req(mask_bits, torch.int64, "mask_bits", numel=P)
+    if agg_needed is not None:
+        _req(agg_needed, torch.bool, "agg_needed", numel=P)
+    if d_agg is not None:
+        _req(d_agg, dt, "d_agg", numel=P * D)
+    dyr = _share_rows(dys, P, D, dt, "dy")
+    dxs = [torch.empty_like(x) for x in dys]
+    dxr = _share_rows(dxs, P, D, dt, "dx")
+    check(lib().m3_share_aggregate_bwd(byref(dyr), dt_code(dt), T, P, D, _p(mask_bits), _p(agg_needed), float(eps), _p(d_agg),
+                                       byref(dxr), _stream()), "m3_share_aggregate_bwd")
+    return dxs
+
+
+def share_compact(bits, num_tasks, prev_bits=None, want_idx=True):
+    """m3_share_compact: (flat_idx int32 [P] ascending then -1, or None; count int32 [1] or None; stats int64
+    [M3_SHARE_STAT_WORDS]) of a shared_bits tensor - all on the device, nothing read back."""
+    _req(bits, torch.int64, "shared_bits")
+    _share_tasks(num_tasks, "share_compact", tmin=1)
+    P = bits.numel()
+    if prev_bits is not None:
+        _req(prev_bits, torch.int64, "prev_shared_bits", numel=P)
+    idx = torch.empty(P, dtype=torch.int32, device=bits.device) if want_idx else None
+    count = torch.empty(1, dtype=torch.int32, device=bits.device) if want_idx else None
+    stats = torch.zeros(SHARE_STAT_WORDS, dtype=torch.int64, device=bits.device)
+    check(lib().m3_share_compact(_p(bits), _p(prev_bits), P, num_tasks, _p(idx), _p(count), _p(stats), _stream()),
+          "m3_share_compact")
+    return idx, count, stats
