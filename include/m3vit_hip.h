@@ -703,7 +703,8 @@ int m3_optim_step(const m3_optim_desc *descs_dev, int n_desc, int total_chunks, 
  * stage of models/heads/vit_up_head.py:181-214 (F.relu(syncbn(conv(x))) then F.interpolate(.., size = 2x, mode='bilinear')).
  * x [N, H, W, C] (x_dtype; C a multiple of 8 for 16-bit, 4 for fp32) -> y [N, 2H, 2W, C] in x's dtype or M3_F32.
  * Backward: dx [N, H, W, C] (x's dtype) = relu'(x) * transpose-resize(dy), dy in x's dtype or M3_F32; a gather over the 4 x 4
- * window of output gradients each input pixel fed (deterministic). */
+ * window of output gradients each input pixel fed (deterministic).  Non-finite inputs give what torch gives (relu(NaN) = NaN,
+ * and the gradient passes where x is NaN) and nothing else moves: a pixel that does not read the Inf / NaN keeps its bits. */
 int m3_relu_up2x_fwd(const void *x, int x_dtype, int64_t N, int H, int W, int C, int relu, void *y, int y_dtype,
                      void *stream);
 int m3_relu_up2x_bwd(const void *dy, int dy_dtype, const void *x, int x_dtype, int64_t N, int H, int W, int C,

@@ -47,7 +47,7 @@ __global__ __launch_bounds__(256) void relu_up2x_fwd_kernel(const T *__restrict_
       Pack<T, NV>::load(base + ((int64_t)rows[a] * W + cols[b]) * C, z[a][b]);
       if (RELU) {
 #pragma unroll
-        for (int j = 0; j < NV; ++j) z[a][b][j] = z[a][b][j] > 0.f ? z[a][b][j] : 0.f;
+        for (int j = 0; j < NV; ++j) z[a][b][j] = z[a][b][j] <= 0.f ? 0.f : z[a][b][j];      // F.relu: a NaN stays a NaN
       }
     }
   // horizontal blends of every row: h[a][0] -> output column 2*ix, h[a][1] -> 2*ix + 1
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void relu_up2x_bwd_kernel(const TG *__restrict
     float xv[NV];
     Pack<T, NV>::load(x + off, xv);
 #pragma unroll
-    for (int j = 0; j < NV; ++j) acc[j] = xv[j] > 0.f ? acc[j] : 0.f;
+    for (int j = 0; j < NV; ++j) acc[j] = xv[j] <= 0.f ? 0.f : acc[j];      // torch's threshold_backward: the gradient passes where x is NaN
   }
   Pack<T, NV>::store(dx + off, acc);
 }

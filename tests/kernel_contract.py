@@ -13,6 +13,9 @@
   allocation, so that its last rows start past 2 or 4 GiB from its base (tests/test_far_operands_gpu.py); check_outside()
   proves that a far output wrote nothing between its rows.
 * topk_agrees() -a kernel's top-k selection against an fp64 top-k, order free only inside the error bound.
+* nonfinite_agrees() / independent_same_bits() - Inf and NaN go through a kernel as through torch: nothing is swallowed (the
+  output is NaN / +-Inf exactly where torch's float64 result on the same poisoned inputs is), nothing leaks (an output that
+  does not depend on the poisoned input keeps the bits of the clean run).
 """
 import math
 
@@ -621,3 +624,78 @@ def gate_bwd_reference(noisy, idx, k, *, clean=None, top_logits=None, idx_next=N
     else:
         ref = torch.zeros_like(nzs)
     return ref, gate_bwd_logits_bound(nzs, dp_abs, dp_err, g_err, ref)
+
+
+# ------------------------------------------------------------------------------------------ Inf and NaN (non-finite inputs)
+FMAX = {torch.float32: float(torch.finfo(torch.float32).max), torch.float16: 65504.0,
+        torch.bfloat16: float(torch.finfo(torch.bfloat16).max)}
+
+
+def _at(j, shape):
+    return tuple(int(v) for v in torch.unravel_index(torch.tensor(j), shape)) if len(shape) else ()
+
+
+def _first(mask):
+    """(flat index of the first True, number of True)"""
+    f = mask.flatten()
+    return int(f.nonzero()[0]), int(f.sum())
+
+
+def nonfinite_agrees(out, ref64, dtype, bound64=None, what="output"):
+    """out (stored as `dtype`) against ref64: torch's own float64 result on the dtype-rounded, poisoned inputs.  Per element
+      ref NaN                                 => out NaN
+      ref +-Inf or |ref| >= 2 max(dtype)      => out is the Inf of that sign (a store that saturates to max(dtype) fails)
+      ref finite, |ref| <= max(dtype) / 2     => out finite, and within bound64 where one is given
+    A finite ref in (1/2, 2) x max(dtype) is a fault of the CASE (fp32 arithmetic may or may not overflow there) and is
+    asserted as such, on the reference.  Returns {"nonfinite": n, "finite": n}: the elements compared in either class."""
+    o = out.detach().double().cpu()
+    r = ref64.detach().double().cpu().expand_as(o)
+    big = FMAX[dtype]
+    grey = torch.isfinite(r) & (r.abs() > big / 2) & (r.abs() < 2 * big)
+    if bool(grey.any()):
+        j, n = _first(grey)
+        raise AssertionError(f"{what}: the case is ill-posed: {n} finite reference value(s) in (1/2, 2) x {big:g}; first at "
+                             f"{_at(j, o.shape)}: ref {float(r.flatten()[j])!r}")
+    want_nan = torch.isnan(r)
+    want_inf = ~want_nan & (r.abs() >= 2 * big)
+    want_fin = ~want_nan & ~want_inf
+    inf_of = torch.where(r > 0, math.inf, -math.inf)
+    bad = (want_nan & ~torch.isnan(o)) | (want_inf & ~(o == inf_of)) | (want_fin & ~torch.isfinite(o))
+    if bool(bad.any()):
+        j, n = _first(bad)
+        rj, oj = float(r.flatten()[j]), float(o.flatten()[j])
+        must = "NaN" if math.isnan(rj) else (f"{float(inf_of.flatten()[j])!r}" if abs(rj) >= 2 * big else "finite")
+        raise AssertionError(f"{what}: {n} of {o.numel()} elements differ from torch on a non-finite input; first at "
+                             f"{_at(j, o.shape)}: got {oj!r}, ref {rj!r}: must be {must}")
+    if bound64 is not None and bool(want_fin.any()):
+        b = torch.as_tensor(bound64).double().cpu().expand_as(o)
+        err = (o - r).abs()
+        over = want_fin & ~(err <= b)
+        if bool(over.any()):
+            j, n = _first(over)
+            raise AssertionError(f"{what}: {n} finite element(s) exceed their bound; first at {_at(j, o.shape)}: got "
+                                 f"{float(o.flatten()[j])!r}, ref {float(r.flatten()[j])!r}, bound {float(b.flatten()[j]):.3e}")
+    return {"nonfinite": int((want_nan | want_inf).sum()), "finite": int(want_fin.sum())}
+
+
+def _bits(t):
+    t = t.detach().contiguous()
+    if t.dtype.is_floating_point:
+        t = t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+    return t.cpu()
+
+
+def independent_same_bits(out_clean, out_poisoned, depends_mask, what="output"):
+    """every element outside depends_mask (bool, broadcastable to the outputs; derived from the OPERATION: "row r of C",
+    "column c of dW of group g", "every token of image b") has the same bits in the clean and in the poisoned run of the
+    same shapes and launch plan.  Returns the number of elements held to it."""
+    assert out_clean.shape == out_poisoned.shape and out_clean.dtype == out_poisoned.dtype, f"{what}: the two runs differ in shape or dtype"
+    a, b = _bits(out_clean), _bits(out_poisoned)
+    dep = torch.as_tensor(depends_mask).cpu().expand_as(a)
+    bad = (a != b) & ~dep
+    if bool(bad.any()):
+        j, n = _first(bad)
+        oc, op = out_clean.detach().contiguous().flatten()[j], out_poisoned.detach().contiguous().flatten()[j]
+        raise AssertionError(f"{what}: {n} element(s) that do not depend on the poisoned input changed; first at "
+                             f"{_at(j, a.shape)}: clean run {float(oc)!r}, poisoned run {float(op)!r}")
+    return int((~dep).sum())

@@ -382,3 +382,88 @@ def test_reach_stride_is_the_last_16_byte_step_under_the_reach():
     ld = kc.reach_stride(300)
     assert 150 * ld < 2 ** 31 < 151 * ld and 299 * ld + 2 * 1024 < 2 ** 32       # rows 151 .. 299 start above 2^31
     assert kc.reach_stride(9, reach=1 << 12) == 400
+
+
+# ------------------------------------------------------------------- Inf / NaN helpers: torch stand-ins for a wrong kernel
+NAN, INF = float("nan"), float("inf")
+
+
+def test_nonfinite_agrees_passes_what_torch_gives_and_counts_the_classes():
+    x = torch.tensor([[NAN, INF, -INF, 1.5], [0.25, -2.0, 3.0, 7e4]])
+    n = kc.nonfinite_agrees(torch.relu(x), torch.relu(x.double()), torch.float32, bound64=0.0)
+    assert n == {"nonfinite": 2, "finite": 6}
+    # an overflowing store: 1e5 in fp16 is Inf; a finite reference in (1/2, 2) x max is the CASE's fault and says so
+    n = kc.nonfinite_agrees(torch.tensor([1.4e5, -1.4e5, 1.0]).half(), torch.tensor([1.4e5, -1.4e5, 1.0]).double(), torch.float16)
+    assert n == {"nonfinite": 2, "finite": 1}
+    with pytest.raises(AssertionError, match=r"ill-posed.*first at \(1,\)"):
+        kc.nonfinite_agrees(torch.tensor([1.0, 7e4]).half(), torch.tensor([1.0, 7e4]).double(), torch.float16)
+    with pytest.raises(AssertionError, match=r"first at \(0, 1\).*must be -inf"):           # the wrong sign of Inf
+        kc.nonfinite_agrees(torch.tensor([[0.0, INF]]), torch.tensor([[0.0, -INF]]).double(), torch.float32)
+    with pytest.raises(AssertionError, match=r"first at \(2,\).*must be finite"):          # a NaN torch does not have
+        kc.nonfinite_agrees(torch.tensor([0.0, 1.0, NAN]), torch.tensor([0.0, 1.0, 2.0]).double(), torch.float32)
+    with pytest.raises(AssertionError, match=r"exceed their bound; first at \(1,\)"):
+        kc.nonfinite_agrees(torch.tensor([NAN, 1.5]), torch.tensor([NAN, 1.0]).double(), torch.float32, bound64=0.25)
+
+
+def test_a_relu_written_as_where_x_gt_0_is_caught_at_the_nan():
+    x = torch.randn(5, 8, generator=torch.Generator().manual_seed(0))
+    x[3, 2], x[1, 1], x[4, 7] = NAN, INF, -INF
+    ref = torch.nn.functional.relu(x.double())
+    kc.nonfinite_agrees(torch.nn.functional.relu(x), ref, torch.float32, bound64=0.0)
+    wrong = torch.where(x > 0, x, torch.zeros_like(x))
+    assert torch.equal(wrong[x == x], torch.relu(x)[x == x])                      # bit-identical on everything but the NaN
+    with pytest.raises(AssertionError, match=r"relu: 1 of 40 elements.*first at \(3, 2\): got 0\.0, ref nan: must be NaN"):
+        kc.nonfinite_agrees(wrong, ref, torch.float32, what="relu")
+
+
+def test_a_tail_mask_written_as_a_product_with_0_is_caught_at_the_leaked_element():
+    """rows 0..5 are the call's, rows 6..7 the padding of its last tile: the sum over the tile's rows masks the padding"""
+    g = torch.Generator().manual_seed(1)
+    tile = torch.randn(8, 4, generator=g)
+    valid = (torch.arange(8) < 6).unsqueeze(1)
+    right = lambda t: torch.where(valid, t, torch.zeros_like(t)).sum(0, keepdim=True)        # noqa: E731
+    wrong = lambda t: (t * valid.float()).sum(0, keepdim=True)                               # noqa: E731
+    poisoned = tile.clone()
+    poisoned[7, 2] = NAN                                                                     # next door, not the call's
+    assert kc.same_bits(right(tile), wrong(tile))                                            # invisible with finite data
+    depends = torch.zeros(1, 4, dtype=torch.bool)                                            # nothing depends on row 7
+    assert kc.independent_same_bits(right(tile), right(poisoned), depends) == 4
+    with pytest.raises(AssertionError, match=r"tile sum: 1 element\(s\).*first at \(0, 2\).*poisoned run nan"):
+        kc.independent_same_bits(wrong(tile), wrong(poisoned), depends, what="tile sum")
+
+
+def test_an_fp16_store_that_clamps_to_65504_is_caught():
+    x = torch.tensor([[1.0, -3.0, 2e5], [-2e5, 2.0, INF]])            # 2e5 >= 2 x 65504: out of the (1/2, 2) x max band
+    ref = x.double()
+    kc.nonfinite_agrees(x.half(), ref, torch.float16, bound64=kc.store(torch.float16, ref))
+    wrong = x.clamp(-65504.0, 65504.0).half()
+    with pytest.raises(AssertionError, match=r"cast: 3 of 6 elements.*first at \(0, 2\): got 65504\.0, ref 200000\.0: must be inf"):
+        kc.nonfinite_agrees(wrong, ref, torch.float16, what="cast")
+
+
+def test_a_grouped_sum_that_reads_the_next_groups_row_with_weight_0_is_caught():
+    """groups of 3, 0 and 2 rows; group g's column sums.  The wrong one walks a tile of 4 rows from the group's first and
+    weighs the rows past its end with 0; poison sits in the first row of the group after the ragged one"""
+    g = torch.Generator().manual_seed(2)
+    rows = torch.randn(5, 4, generator=g)
+    off = [0, 3, 3, 5]
+
+    def right(r):
+        return torch.stack([r[off[i]:off[i + 1]].sum(0) for i in range(3)])
+
+    def wrong(r):
+        padded = torch.cat((r, torch.zeros(4, 4)))
+        return torch.stack([(padded[off[i]:off[i] + 4] * (torch.arange(4) < off[i + 1] - off[i]).float().unsqueeze(1)).sum(0)
+                            for i in range(3)])
+
+    poisoned = rows.clone()
+    poisoned[3, 1] = INF                                                                     # first row of group 2
+    assert torch.allclose(right(rows), wrong(rows))
+    depends = torch.zeros(3, 4, dtype=torch.bool)
+    depends[2, 1] = True                                                                     # column 1 of group 2, nothing else
+    assert kc.independent_same_bits(right(rows), right(poisoned), depends) == 11
+    kc.nonfinite_agrees(right(poisoned), right(poisoned.double()), torch.float32)
+    with pytest.raises(AssertionError, match=r"group sums: 2 element\(s\).*first at \(0, 1\): clean run .* poisoned run nan"):
+        kc.independent_same_bits(wrong(rows), wrong(poisoned), depends, what="group sums")
+    with pytest.raises(AssertionError, match=r"first at \(0, 1\): got nan, ref .*: must be finite"):
+        kc.nonfinite_agrees(wrong(poisoned), right(poisoned.double()), torch.float32)
