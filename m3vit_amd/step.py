@@ -18,6 +18,10 @@ Expert-parallel runs (ep_world > 1) read each MoE layer's exchange split sizes o
 their task passes still get a stream each, with their blocks interleaved on the host (_ep_interleaved)."""
 from __future__ import annotations
 
+import os
+from functools import partial
+from types import SimpleNamespace
+
 import torch
 
 from . import ops
@@ -103,6 +107,10 @@ class MultiTaskStep:
         self.stem = self.eng.stem_blocks if self.share_stem else 0
         # the gradient add runs under the stem's backward on the (then idle) first task stream: no stream of its own
         self.add_stream = self.streams[0] if self.share_stem else None
+        # ... over flat[lo_j:add_cuts[j]], part j's gradients above the stem boundary (the contexts of the other passes never
+        # ran a stem: their slices below it are zero)
+        stem_prefix = self.eng.grad_prefix(self.stem)
+        self.add_cuts = [min(hi, max(lo, stem_prefix)) for lo, hi in self.segments]
         self.late_names = [n for n in self.eng.params if self.eng._block_of(n) < 0 and
                            not n.startswith(("patch_embed.", "cls_token", "dist_token", "pos_embed"))]
         # the part whose block range first reaches below the stem boundary takes the other passes' d x
@@ -116,7 +124,6 @@ class MultiTaskStep:
         # in profiles/r02_wgrad_capture_segv.txt): the runtime's fault, not the engine's event use.  That combination is
         # refused here and runs eagerly.
         self.capture_refused = None
-        import os
         if self.use_ep:
             import torch.distributed as dist
             # the fixed-capacity exchange reads nothing on the host inside the step, so a collective library whose calls
@@ -124,28 +131,23 @@ class MultiTaskStep:
             if not (self.ep_capacity and os.environ.get("M3_EP_CAPTURE") == "1" and dist.get_backend() == "nccl"):
                 self.capture_refused = ("expert-parallel steps read the exchange's split sizes on the host" if not self.ep_capacity
                                         else "fixed-capacity expert-parallel step: capture is opt-in (M3_EP_CAPTURE=1, backend nccl)")
-        elif wg and self.par and (self.share_stem or not (os.environ.get("M3_LINEAR_GRAPHS", "auto") == "1" or (os.environ.get("M3_LINEAR_GRAPHS", "auto") == "auto" and self.world == 1)) or
-                                  os.environ.get("M3_WGRAD_STREAMS_CAPTURE", "0") != "1"):
-            # (with one linear graph per task pass - _capture_linear - a pass's wgrad stream is forked from that pass's OWN
-            # capturing stream, which is the pattern that works; opt-in M3_WGRAD_STREAMS_CAPTURE=1 until measured)
+        elif wg and self.par:
+            # (capture() keeps the weight-gradient launches on the capturing stream, so a graph of this step would be the graph
+            # of a step without wgrad streams; the form with them forked per pass measured 19.97 against 16.87 ms,
+            # profiles/r04_levers_measured_and_dropped.txt)
             self.capture_refused = ("wgrad streams forked from forked task streams: hipStreamEndCapture (ROCm 7.2) segfaults on "
                                     "a nested fork (engine-free reproducer: tools/nested_capture_probe.py); use serial tasks or "
                                     "no wgrad streams to replay a graph")
         self.want_graph = bool(graph) and self.capture_refused is None
-        # side-by-side passes are captured as one linear graph per pass and stream (_capture_linear), the shared stem's gradient
-        # add and stem backward as two more per part.  A shared stem cut into data-parallel parts used to keep one graph per part
-        # with the streams forked inside the capture: replaying that graph segfaulted on the host, in CUDAGraph.replay (ROCm 7.2;
-        # tests/test_engine.py::test_shared_stem_step_matches_per_task_stems), so it is captured linearly as well
-        import os as _os
-        # (also at N > 1 since round 5, one linear graph per (part, pass).  Round 4 turned this off there because the only
-        # multi-rank run this build box allows - two PROCESSES on one GPU over gloo - stalled for seconds per step with it;
-        # profiles/r05_dp_two_rank_stream_count.txt found the cause: the two processes' streams outnumber the hardware queues
-        # HIP maps them to by default (one task stream per step is slower still, 8 757 ms; twice the queues -> 103 ms per
-        # step against 130 for the one-graph-per-part form).  One rank per GPU never shares queues; the one-device rehearsals
-        # (bench.py M3_BENCH_ONE_DEVICE, tests) share them.  M3_LINEAR_GRAPHS=0 restores one graph per part.)
-        lin = _os.environ.get("M3_LINEAR_GRAPHS", "auto")
-        self.linear_graphs = self.par and lin != "0"
+        # Side-by-side passes are captured piece by piece, every piece a linear graph of its own (capture(), _walk), at every
+        # world size.  One graph per part with the streams forked inside the capture is not an option: replaying it segfaulted
+        # on the host, in CUDAGraph.replay (ROCm 7.2; tests/test_engine.py::test_shared_stem_step_matches_per_task_stems), and
+        # cost the host ~14 ms per step (capture()).  Two PROCESSES on one GPU over gloo (bench.py M3_BENCH_ONE_DEVICE, tests)
+        # can stall for seconds per step with the linear graphs: their streams outnumber the hardware queues HIP maps them to
+        # by default (profiles/r05_dp_two_rank_stream_count.txt; twice the queues -> 103 ms per step).  One rank per GPU never
+        # shares queues.
         self.graphs = None
+        self._pieces, self._anchor = {}, None            # the captured pieces {(part, name): graph} and the tensor they own
         self.capture_error = None
         self.images = self.dtok = self.noises = self.logit_bias = None
 
@@ -280,38 +282,53 @@ class MultiTaskStep:
             for e in self.engs:
                 e.ep_fixed = True
 
+    def _walk(self, j: int, do):
+        """Part j of the side-by-side step: its pieces, their order and the stream each is issued on, stated once for the
+        three users.  do(name, fn) is called with the piece's stream current: part() runs fn, capture() captures fn into a
+        graph of the piece's own, a captured part replays that graph.  (The engines' host-side backward state follows this
+        order, so a capture must issue the pieces as an eager step does.)  A piece without a name is launched eagerly
+        between the graphs.  The forks and joins are placed here, outside every piece."""
+        def prep():
+            self.eng.prepare_weights()
+            if self.share_stem:                  # the task-independent stem once, before the passes fork
+                self.eng.zero_grad()
+                self.eng.forward_stem(self.images)
+
+        def stem():
+            self._stem_backward(j)
+            if j == len(self.block_ranges) - 1:
+                # parameters outside the blocks that are NOT part of the stem (the task-embedding MLP of a task-conditioned
+                # gate): every pass has its own (small) gradient there; pass 0's was completed by the backward_end() just above
+                for n in self.late_names:
+                    for e in self.engs[1:]:
+                        ops.add_f32(self.eng.grads[n].view(-1), e.grads[n].view(-1))
+
+        if j == 0:
+            do("prep", prep)
+        run = self._part(j)
+        self._run_tasks(lambda e, t: do(f"pass{self.engs.index(e)}", lambda: run(e, t)))
+        lo, hi = self.segments[j]
+        if not self.share_stem:
+            do(None, lambda: self._add(lo, hi))
+            return
+        # the other passes' gradients of this part (final now) are added on the idle first task stream while the stem's share
+        # of the part runs once on the summed d x
+        cut = self.add_cuts[j]
+        main = torch.cuda.current_stream()
+        self.add_stream.wait_stream(main)
+        if cut > lo:
+            with torch.cuda.stream(self.add_stream):
+                do("add", lambda: self._add(lo, cut))
+        do("stem", stem)
+        main.wait_stream(self.add_stream)
+
     def part(self, j: int):
         """part j of the step on the current stream (part 0 alone is the whole step unless the step is cut)"""
         if self.par_ep:
             return self._ep_interleaved()
         if not self.par:
             return self.serial_step()
-        if j == 0:
-            self.eng.prepare_weights()
-            if self.share_stem:
-                self.eng.zero_grad()
-                self.eng.forward_stem(self.images)
-        self._run_tasks(self._part(j))
-        if not self.share_stem:
-            self._add(*self.segments[j])
-            return
-        # the other passes' gradients of this part (final now; none of them below the stem boundary - those contexts never
-        # ran a stem, their slices there are zero) are added on a side stream while the stem's backward runs
-        lo, hi = self.segments[j]
-        cut = min(hi, max(lo, self.eng.grad_prefix(self.stem)))
-        main = torch.cuda.current_stream()
-        self.add_stream.wait_stream(main)
-        with torch.cuda.stream(self.add_stream):
-            if cut > lo:
-                self._add(lo, cut)
-        self._stem_backward(j)
-        if j == len(self.block_ranges) - 1:
-            # parameters outside the blocks that are NOT part of the stem (the task-embedding MLP of a task-conditioned gate):
-            # every pass has its own (small) gradient there; pass 0's was completed by the backward_end() just above
-            for n in self.late_names:
-                for e in self.engs[1:]:
-                    ops.add_f32(self.eng.grads[n].view(-1), e.grads[n].view(-1))
-        main.wait_stream(self.add_stream)
+        self._walk(j, lambda name, fn: fn())
 
     def compute(self):
         for j in range(len(self.block_ranges)):
@@ -348,85 +365,6 @@ class MultiTaskStep:
     def step_eager(self):
         self._collective_step([lambda j=j: self.part(j) for j in range(len(self.block_ranges))])
 
-    def _capture_linear(self):
-        """One LINEAR hipGraph per (part, task pass), replayed on that pass's own stream, instead of one graph per part with
-        the passes forked inside the capture.  Same kernels in the same per-stream order, but the host's replay cost falls
-        from ~14 ms to ~0.25 ms per step (a graph whose branches run on several streams is launched node by node with
-        events between the branches; a linear one is one submission - tools/graph_per_stream_probe.py): with a trainer that
-        synchronises every step (it reads the loss) the step is 0.4 ms shorter, the host never becomes the limiter, and at
-        N > 1 the all-reduce behind a part is issued the moment the part is queued."""
-        nparts = len(self.block_ranges)
-        # a shared stem cut into parts has (part, pass) pieces that launch nothing (a part below a pass's own blocks, the
-        # stem's share of a part above it): each of its graphs starts with a one-element write so that none is empty
-        anchor = torch.zeros(1, device=self.dev) if (self.share_stem and nparts > 1) else None
-
-        def graph_of(fn, *a):
-            g = torch.cuda.CUDAGraph()
-            with ops.graph_capture(g):
-                if anchor is not None:
-                    anchor.zero_()
-                fn(*a)
-            return g
-
-        def prep_fn():
-            self.eng.prepare_weights()
-            if self.share_stem:                  # the task-independent stem once, before the passes fork (see part())
-                self.eng.zero_grad()
-                self.eng.forward_stem(self.images)
-
-        def post_fn(j):
-            self._stem_backward(j)
-            if j == nparts - 1:
-                for n in self.late_names:
-                    for e in self.engs[1:]:
-                        ops.add_f32(self.eng.grads[n].view(-1), e.grads[n].view(-1))
-        prep = graph_of(prep_fn)
-        # captured in the order part() issues the launches (the engines' host-side backward state follows that order)
-        per, add_gs, post_gs = [], [None] * nparts, [None] * nparts
-        for j in range(nparts):
-            fn = self._part(j)
-            per.append([graph_of(fn, e, t) for e, t in zip(self.engs, self.tasks)])
-            if self.share_stem:
-                # behind the part's join: the other passes' gradients of the part above the stem boundary are added on the
-                # idle first task stream while the stem's share of the part runs once on the summed d x - as two more linear
-                # graphs (same launches as part()'s tail)
-                lo, hi = self.segments[j]
-                cut = min(hi, max(lo, self.eng.grad_prefix(self.stem)))
-                if cut > lo:
-                    add_gs[j] = graph_of(self._add, lo, cut)
-                post_gs[j] = graph_of(post_fn, j)
-        step = self
-
-        class PartReplay:
-            def __init__(self, j):
-                self.j = j
-
-            def replay(self):
-                j = self.j
-                main = torch.cuda.current_stream()
-                if j == 0:
-                    prep.replay()
-                for st in step.streams:
-                    st.wait_stream(main)
-                per[j][0].replay()
-                for st, g in zip(step.streams, per[j][1:]):
-                    with torch.cuda.stream(st):
-                        g.replay()
-                for st in step.streams:
-                    main.wait_stream(st)
-                if not step.share_stem:
-                    step._add(*step.segments[j])
-                    return
-                step.add_stream.wait_stream(main)
-                if add_gs[j] is not None:
-                    with torch.cuda.stream(step.add_stream):
-                        add_gs[j].replay()
-                post_gs[j].replay()
-                main.wait_stream(step.add_stream)
-
-        self._linear_keep = (prep, per, add_gs, post_gs, anchor)
-        return [PartReplay(j) for j in range(nparts)]
-
     def capture(self) -> bool:
         """Capture the compute of a step into hipGraph(s).  Returns False (and stays eager) if capture is unavailable."""
         if not self.want_graph:
@@ -446,16 +384,44 @@ class MultiTaskStep:
             # graph is linear; eager steps keep their wgrad streams.
             for e in self.engs:
                 e.wg_stream = None
-            if self.linear_graphs:
-                self.graphs = self._capture_linear()
+            # One LINEAR hipGraph per piece of _walk - per (part, task pass), replayed on that pass's own stream - instead of one
+            # graph per part with the passes forked inside the capture.  Same kernels in the same per-stream order, but the
+            # host's replay cost falls from ~14 ms to ~0.25 ms per step (a graph whose branches run on several streams is launched
+            # node by node with events between the branches; a linear one is one submission - tools/graph_per_stream_probe.py):
+            # with a trainer that synchronises every step (it reads the loss) the step is 0.4 ms shorter, the host never
+            # becomes the limiter, and at N > 1 the all-reduce behind a part is issued the moment the part is queued.
+            # A shared stem cut into parts has (part, pass) pieces that launch nothing (a part below a pass's own blocks, the
+            # stem's share of a part above it): each of its graphs starts with a one-element write so that none is empty.
+            nparts = len(self.block_ranges)
+            anchor = torch.zeros(1, device=self.dev) if (self.share_stem and nparts > 1) else None
+            pieces = {}
+
+            def graph_of(fn):
+                g = torch.cuda.CUDAGraph()
+                with ops.graph_capture(g):
+                    if anchor is not None:
+                        anchor.zero_()
+                    fn()
+                return g
+
+            def capture_piece(j, name, fn):
+                if name is not None:
+                    pieces[j, name] = graph_of(fn)
+
+            def replay_piece(j, name, fn):
+                if name is None:
+                    fn()
+                else:
+                    pieces[j, name].replay()
+
+            if not self.par:       # never cut: the serial step, or an expert-parallel step that __init__ let through
+                self.graphs = [graph_of(lambda: self.part(0))]
                 return True
-            graphs = []
-            for j in range(len(self.block_ranges)):
-                gj = torch.cuda.CUDAGraph()
-                with ops.graph_capture(gj):
-                    self.part(j)
-                graphs.append(gj)
-            self.graphs = graphs
+            # (the forks and joins of _walk fall between the captures here, where they order nothing)
+            for j in range(nparts):
+                self._walk(j, partial(capture_piece, j))
+            self._pieces, self._anchor = pieces, anchor
+            self.graphs = [SimpleNamespace(replay=partial(self._walk, j, partial(replay_piece, j))) for j in range(nparts)]
             return True
         except Exception as exc:   # capture is an optimisation, never a requirement - but say why it was lost
             import sys
@@ -482,4 +448,4 @@ class MultiTaskStep:
     def launch(self) -> str:
         if self.graphs is None:
             return "eager"
-        return "hipGraph replay (one linear graph per task pass and stream)" if self.linear_graphs else "hipGraph replay"
+        return "hipGraph replay (one linear graph per task pass and stream)" if self.par else "hipGraph replay"

@@ -1,16 +1,17 @@
 # ONE two-rank rehearsal per setting (two PROCESSES on one MI355X over gloo, data-parallel leg with one linear
 # hipGraph per task pass - the form that stalled for seconds per step in round 4) with the number of HIP streams per process
 # varied: (a) two task streams per process as benchmarked at N = 1, (b) the task passes folded onto ONE stream
-# (--serial-tasks), (c) two task streams with one graph per part.  The hardware-queue count is the runtime's own setting
-# (the round-5 record in profiles/r05_dp_two_rank_stream_count.txt also varied it).
+# (--serial-tasks).  The hardware-queue count is the runtime's own setting (the round-5 record in
+# profiles/r05_dp_two_rank_stream_count.txt also varied it, and had a case (c), one graph per part, a form the step runner no
+# longer has).
 #   tools/dp_two_rank_streams.sh <out-file>
 R=$GRAFT_REPO_ROOT
 OUT=$R/$1
-export M3_BENCH_BACKEND=gloo M3_BENCH_ONE_DEVICE=1 M3_LINEAR_GRAPHS=1 M3_BENCH_NO_AGREE=0
+export M3_BENCH_BACKEND=gloo M3_BENCH_ONE_DEVICE=1 M3_BENCH_NO_AGREE=0
 run() {
-  tag=$1; envs=$2; flags=$3
-  echo "=== $tag: env $envs flags $flags" >> $OUT
-  ( cd $R && timeout -k 10 240 env $envs python bench.py --gpus 2 --dp-only --steps 20 --warmup 3 --no-cpu-baseline $flags > /tmp/two_rank.json 2> /tmp/two_rank.err )
+  tag=$1; flags=$2
+  echo "=== $tag: flags $flags" >> $OUT
+  ( cd $R && timeout -k 10 240 python bench.py --gpus 2 --dp-only --steps 20 --warmup 3 --no-cpu-baseline $flags > /tmp/two_rank.json 2> /tmp/two_rank.err )
   echo "rc=$?" >> $OUT
   python - >> $OUT <<PY
 import json
@@ -23,6 +24,5 @@ PY
   grep -h "timed region\|host launch\|FAILED\|Error" /tmp/two_rank.err | tail -6 >> $OUT
 }
 : > $OUT
-run "(a) two task streams per process, linear graphs" "M3_LINEAR_GRAPHS=1" ""
-run "(b) task passes folded onto ONE stream per process" "M3_LINEAR_GRAPHS=1" "--serial-tasks"
-run "(c) two task streams, one graph per part (M3_LINEAR_GRAPHS=0)" "M3_LINEAR_GRAPHS=0" ""
+run "(a) two task streams per process, linear graphs" ""
+run "(b) task passes folded onto ONE stream per process" "--serial-tasks"
