@@ -1084,6 +1084,66 @@ int m3_share_aggregate_bwd(const m3_share_rows *dy, int dtype, int T, int64_t P,
 int m3_share_compact(const int64_t *shared_bits, const int64_t *prev_shared_bits, int64_t P, int T, int32_t *shared_flat_idx,
                      int32_t *count, int64_t *stats, void *stream);
 
+/* ------------------------------------------------------------------------------------- token blocks: the FFN sublayer
+ * Step 5 of TokenBlock.forward (models/moe/token/vision_transformer_moe.py) for the blocks that need no router, over the
+ * rows that differ only: the private rows of every task and ONE row per shared position.
+ *   mode M3_TOKEN_FFN_ALL     the dense block: dense_mlp_stage(outs, shared_bits), shared_dense_forward(shared_x),
+ *                             apply_shared_broadcast (:443-515, :966-984) - private and shared rows, one weight set
+ *   mode M3_TOKEN_FFN_SHARED  the shared branch of an MoE block: shared_x + drop_path(shared_ffn(norm2(shared_x))), then the
+ *                             broadcast (:1002-1014) - shared rows only, private rows pass through
+ * With private(t, p) = bit t of bits[p] clear and F(v) = fc2(gelu(fc1(LayerNorm(v)))):
+ *   shared_out[p] = shared_x[p] + shared_path_scale[p] * F(shared_x[p])         where bits[p] != 0
+ *   y_t[p]        = x_t[p] + path_scale[p / N] * F(x_t[p])                      where private(t, p), mode ALL
+ *   y_t[p]        = x_t[p] (its own bits)                                       where private(t, p), mode SHARED
+ *   y_t[p]        = shared_out[p]                                               where bit t of bits[p] is set
+ * Dense form: no early return, no nonzero(), no host read; the row count R stays on the device and every buffer and launch
+ * is sized by the bound m3_token_ffn_rows_ub = T * P (ALL) or P (SHARED): a position whose word has at most one bit set
+ * contributes T rows, any other T - popcount + 1 <= T - 1.  Task tensors are m3_share_rows tables as in the sharing stage;
+ * the same limits (2 <= T <= M3_SHARE_MAX_T, D a multiple of 8 in [8, M3_SHARE_MAX_D]: M3_ERR_UNSUPPORTED) and
+ * (T + 1) * P < 2^31 (M3_ERR_ARG).  Bits of a word at and above T are ignored.  No atomics: the same bits from run to run.
+ *
+ * m3_token_ffn_worklist: work row r of segment seg <= T at position p has the entry rows[r] = seg * P + p; segment t < T
+ *   lists the private positions of task t (mode ALL; empty in mode SHARED), segment T the positions with bits != 0;
+ *   segment-major, ascending p.  rows i32 [M_ub]: entries [0, R) are written, the rest is left alone.  slot_of i32 [T + 1][P]:
+ *   the inverse, -1 for a (segment, position) that is not listed.  offsets, tile_starts i32 [2] = {0, R}, {0, ceil(R / 128)}:
+ *   exactly what m3_route_build writes for one group (it is what writes them), so m3_gemm_nt / m3_wgrad_tn take them as
+ *   group_offsets / tile_starts with G = 1.  count i32 [1] = R.  ws i32 [m3_token_ffn_list_ws_elems(P, T)], no initialisation.
+ * m3_token_ffn_ln_fwd (norm2 of the listed rows, gathered): h[r] = LayerNorm(source row of work row r) * gamma + beta into
+ *   the compact [M_ub][D] buffer (activation dtype), mean / rstd f32 [M_ub]; two-pass variance in fp32.  Rows at and past
+ *   count are neither read nor written.
+ * (fc1 / fc2, Mlp.forward token/layers.py: m3_gemm_nt with G = 1 and the work list's offsets.)
+ * m3_token_ffn_scatter_fwd (the residual adds of dense_mlp_stage / shared_dense_forward and apply_shared_broadcast): one
+ *   pass over the positions writes every y_t[p] by the formulas above from x_t, shared_x, f [M_ub][D] = F of the work rows,
+ *   slot_of and the DropPath factors path_scale f32 [P / N] (the reference's one mask per block and sample) and
+ *   shared_path_scale f32 [P] (its DropPath over the compact [K, C] tensor: per shared row); NULL = 1.
+ * m3_token_ffn_gather_bwd: d f[r] = path_scale * d y_t[p] for a private row, shared_path_scale[p] * (sum over the set bits,
+ *   t ascending, of d y_t[p]) for a shared row, rounded once to the activation dtype; rows at and past count untouched.
+ * m3_token_ffn_scatter_bwd: from d h [M_ub][D] (the gradient at the LayerNorm's output: fc1's dgrad) writes every
+ *   d x_t[p] = d y_t[p] (+ the LayerNorm backward of d h[slot] where the row is listed), EXACT zero where the broadcast
+ *   overwrote the row, and d shared_x[p] = sum over the set bits of d y_t[p] + the LayerNorm backward of its d h row, exact
+ *   zero where bits[p] == 0; d_gamma, d_beta f32 [D] (overwritten) from one partial row per workgroup added in a fixed order
+ *   by a second launch.  ws f32 [m3_token_ffn_bwd_ws_elems(P, D)], no initialisation. */
+#define M3_TOKEN_FFN_ALL 0
+#define M3_TOKEN_FFN_SHARED 1
+int64_t m3_token_ffn_rows_ub(int64_t P, int T, int mode);
+int64_t m3_token_ffn_list_ws_elems(int64_t P, int T);
+int64_t m3_token_ffn_bwd_ws_elems(int64_t P, int D);
+int m3_token_ffn_worklist(const int64_t *bits, int64_t P, int T, int mode, int32_t *rows, int32_t *slot_of,
+                          int32_t *offsets, int32_t *tile_starts, int32_t *count, int32_t *ws, void *stream);
+int m3_token_ffn_ln_fwd(const m3_share_rows *x, const void *shared_x, int dtype, int T, int64_t P, int D,
+                        const int32_t *rows, const int32_t *count, int64_t M_ub, const float *gamma, const float *beta,
+                        float eps, void *h, float *mean, float *rstd, void *stream);
+int m3_token_ffn_scatter_fwd(const m3_share_rows *x, const void *shared_x, const void *f, int dtype, int T, int64_t P,
+                             int N, int D, int mode, const int32_t *slot_of, const int64_t *bits, const float *path_scale,
+                             const float *shared_path_scale, const m3_share_rows *y, void *stream);
+int m3_token_ffn_gather_bwd(const m3_share_rows *dy, int dtype, int T, int64_t P, int N, int D, const int32_t *rows,
+                            const int32_t *count, int64_t M_ub, const int64_t *bits, const float *path_scale,
+                            const float *shared_path_scale, void *df, void *stream);
+int m3_token_ffn_scatter_bwd(const m3_share_rows *x, const void *shared_x, const m3_share_rows *dy, const void *dh,
+                             const float *mean, const float *rstd, int dtype, int T, int64_t P, int D, int mode,
+                             const int32_t *slot_of, const int64_t *bits, const float *gamma, const m3_share_rows *dx,
+                             void *d_shared_x, float *ws, float *d_gamma, float *d_beta, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

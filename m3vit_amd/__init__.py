@@ -26,7 +26,8 @@ _LOSS_NAMES = ("SoftMaxwithLoss", "BalancedCrossEntropyLoss", "DepthLoss", "Norm
                "get_loss")
 _METER_NAMES = ("PerformanceMeter", "SemsegMeter", "HumanPartsMeter", "DepthMeter", "NormalsMeter", "SaliencyMeter", "EdgeMeter",
                 "AverageMeter", "get_single_task_meter", "calculate_multi_task_performance", "get_output")
-_SHARING_NAMES = ("ShareabilityPredictor", "Aggregation", "AggregationStage", "SharingRegularizationLoss", "SharingStage")
+_SHARING_NAMES = ("ShareabilityPredictor", "Aggregation", "AggregationStage", "SharingRegularizationLoss", "SharingStage",
+                  "TokenFFNStage")
 
 
 def __getattr__(name):

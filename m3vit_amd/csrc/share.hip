@@ -15,13 +15,12 @@
 //   M_t = G_t >= gamma, dropped where fewer than 2 tasks agree;  den = (sum_t G_t M_t, t ascending) + eps;  W_t = G_t M_t / den
 //   shared_x = fma chain over t ascending of W_t x_t, rounded once to the activation dtype; y_t = that value or x_t's own bits
 // No atomics anywhere: the parameter gradients are per-workgroup partials added in a fixed order by one reduce launch.
-#include "common.h"
+#include "share_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace m3 {
 
-constexpr int SHARE_CH = 8;                         // elements per lane chunk
 constexpr int SHARE_SCAN = M3_SHARE_SCAN_WIDTH;     // positions per step of the compaction scan = its workgroup size
 
 struct ShareFwdDev {
@@ -46,33 +45,6 @@ struct ShareAggDev {
   int64_t P; int D;
   const int64_t *mask; const unsigned char *need; float eps;
   void *agg;                                        // forward: the dense mean (optional); backward: d agg (optional)
-};
-
-// ------------------------------------------------------------------------------------------------ the lane's view of a row
-template <typename T, int NCH> struct RowIO {
-  // chunk i of this lane starts at element off[i]; chunks past D read chunk 0 (an address that exists) and become zeros
-  static __device__ __forceinline__ void load(const void *row, int D, int lane, float (&v)[NCH][SHARE_CH]) {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int d = (lane + 64 * i) * SHARE_CH;
-      Pack<T, SHARE_CH>::load((const T *)row + (d < D ? d : 0), v[i]);
-    }
-  }
-  static __device__ __forceinline__ void mask(int D, int lane, float (&v)[NCH][SHARE_CH]) {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const bool ok = (lane + 64 * i) * SHARE_CH < D;
-#pragma unroll
-      for (int j = 0; j < SHARE_CH; ++j) v[i][j] = ok ? v[i][j] : 0.f;
-    }
-  }
-  static __device__ __forceinline__ void store(void *row, int D, int lane, const float (&v)[NCH][SHARE_CH]) {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const int d = (lane + 64 * i) * SHARE_CH;
-      if (d < D) Pack<T, SHARE_CH>::store((T *)row + d, v[i]);
-    }
-  }
 };
 
 // the lane's slice of w_gate [D + Dg][2] (rows d of its chunks): column 0 and column 1

@@ -563,3 +563,57 @@ class ShareAggregateFn(torch.autograd.Function):
         dys = [d.contiguous() for d in grads[:T]]
         dxs = ops.share_aggregate_bwd(dys, mask_bits, agg_needed, ctx.eps, grads[T].contiguous())
         return (None, None, None, *[d.view(s) for d, s in zip(dxs, ctx.shapes)])
+
+
+class TokenFFNFn(torch.autograd.Function):
+    """The second sublayer of a TokenBlock over private and shared rows only, as ONE node (token/vision_transformer_moe.py:
+    dense_mlp_stage + shared_dense_forward + apply_shared_broadcast :443-515, :966-984 in mode "all"; the shared_ffn branch
+    and its broadcast :1002-1014 in mode "shared"): work list -> LayerNorm-gather -> FC1 (+bias, GELU) -> FC2 (+bias) as
+    grouped GEMMs with ONE group whose row count lives on the device -> scatter; the backward the same chain in reverse.
+    apply(bits int64 [P], gamma, beta, eps, w1, b1, w2, b2, path_scale f32 [B] or None, shared_path_scale f32 [P] or None,
+          mode, tokens_per_sample, shared_x [P, D], *xs) -> ys"""
+
+    @staticmethod
+    def forward(ctx, bits, gamma, beta, eps, w1, b1, w2, b2, path_scale, shared_path_scale, mode, N, sx, *xs):
+        xs = [x.detach().contiguous() for x in xs]
+        sx = sx.detach().contiguous()
+        dt, dev, T = xs[0].dtype, xs[0].device, len(xs)
+        ga, be = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+        wl = ops.token_ffn_worklist(bits, T, mode)
+        h, mean, rstd = ops.token_ffn_ln_fwd(xs, sx, wl, ga, be, eps)
+        M, H, C = wl.M_ub, w1.shape[0], w2.shape[0]
+        pre = torch.empty(M, H, dtype=dt, device=dev)
+        u = torch.empty_like(pre)
+        ops.gemm_nt(h, _wcopy(w1, dt), u, M=M, bias=b1.detach(), act=M3_ACT_GELU, pre_out=pre, group_offsets=wl.offsets,
+                    tile_starts=wl.tile_starts)
+        f = torch.empty(M, C, dtype=dt, device=dev)
+        ops.gemm_nt(u, _wcopy(w2, dt), f, M=M, bias=b2.detach(), group_offsets=wl.offsets, tile_starts=wl.tile_starts)
+        ys = ops.token_ffn_scatter_fwd(xs, sx, f, wl, bits, N, path_scale, shared_path_scale)
+        ctx.save_for_backward(bits, ga, w1, w2, path_scale, shared_path_scale, sx, h, mean, rstd, pre, u, wl.rows, wl.slot_of,
+                              wl.offsets, wl.tile_starts, wl.count, *xs)
+        ctx.mode, ctx.N, ctx.shapes, ctx.sx_shape = mode, N, [x.shape for x in xs], sx.shape
+        return tuple(y.view(s) for y, s in zip(ys, ctx.shapes))
+
+    @staticmethod
+    def backward(ctx, *grads):
+        bits, ga, w1, w2, ps, sps, sx, h, mean, rstd, pre, u, rows, slot_of, offsets, tile_starts, count, *xs = ctx.saved_tensors
+        dt, dev, T = xs[0].dtype, xs[0].device, len(xs)
+        wl = ops.TokenWorkList()
+        wl.rows, wl.slot_of, wl.offsets, wl.tile_starts, wl.count = rows, slot_of, offsets, tile_starts, count
+        wl.P, wl.T, wl.mode, wl.M_ub = bits.numel(), T, ctx.mode, rows.numel()
+        M = wl.M_ub
+        dys = [_grad_like(g, xs[0]).reshape(x.shape) for g, x in zip(grads, xs)]
+        df = ops.token_ffn_gather_bwd(dys, wl, bits, ctx.N, ps, sps)
+        dw2 = torch.empty(w2.shape, dtype=torch.float32, device=dev)
+        db2 = torch.empty(w2.shape[0], dtype=torch.float32, device=dev)
+        ops.wgrad_tn(df, u, dw2, M=M, group_offsets=offsets, db=db2)            # bias grad in the same pass
+        dpre = torch.empty_like(pre)
+        ops.gemm_nt(df, _wcopy(w2, dt, transpose=True), dpre, M=M, gelu_grad_pre=pre, group_offsets=offsets, tile_starts=tile_starts)
+        dw1 = torch.empty(w1.shape, dtype=torch.float32, device=dev)
+        db1 = torch.empty(w1.shape[0], dtype=torch.float32, device=dev)
+        ops.wgrad_tn(dpre, h, dw1, M=M, group_offsets=offsets, db=db1)
+        dh = torch.empty_like(h)
+        ops.gemm_nt(dpre, _wcopy(w1, dt, transpose=True), dh, M=M, group_offsets=offsets, tile_starts=tile_starts)
+        dxs, d_sx, dg, dbeta = ops.token_ffn_scatter_bwd(xs, sx, dys, dh, mean, rstd, wl, bits, ga)
+        return (None, dg, dbeta, None, dw1, db1, dw2, db2, None, None, None, None, d_sx.view(ctx.sx_shape),
+                *[d.view(s) for d, s in zip(dxs, ctx.shapes)])

@@ -1984,3 +1984,139 @@ def share_compact(bits, num_tasks, prev_bits=None, want_idx=True):
     check(lib().m3_share_compact(_p(bits), _p(prev_bits), P, num_tasks, _p(idx), _p(count), _p(stats), _stream()),
           "m3_share_compact")
     return idx, count, stats
+
+
+# ----------------------------------------------------------------------------- token blocks: FFN sublayer (csrc/token_ffn.hip)
+TOKEN_FFN_MODES = {"all": _lib.M3_TOKEN_FFN_ALL, "shared": _lib.M3_TOKEN_FFN_SHARED}
+
+
+def _token_ffn_mode(mode):
+    try:
+        return TOKEN_FFN_MODES[mode]
+    except KeyError:
+        raise _lib.M3Error(f"token FFN: mode {mode!r} is neither 'all' nor 'shared'")
+
+
+def token_ffn_rows_ub(P, T, mode) -> int:
+    """the bound on the work rows every buffer and launch is sized by: T * P (mode 'all'), P (mode 'shared')"""
+    return int(lib().m3_token_ffn_rows_ub(P, T, _token_ffn_mode(mode)))
+
+
+class TokenWorkList:
+    """Device-resident work list of the token FFN (m3_token_ffn_worklist in include/m3vit_hip.h; no host sync):
+    rows i32 [M_ub], slot_of i32 [T + 1, P] (-1: not listed), offsets / tile_starts i32 [2] (group_offsets / tile_starts of a
+    grouped GEMM with G = 1), count i32 [1]."""
+    __slots__ = ("rows", "slot_of", "offsets", "tile_starts", "count", "M_ub", "P", "T", "mode")
+
+
+def token_ffn_worklist(bits, T, mode, *, rows=None, slot_of=None, ws=None) -> TokenWorkList:
+    """m3_token_ffn_worklist of a shared_bits tensor int64 [P]"""
+    _req(bits, torch.int64, "shared_bits")
+    _share_tasks(T, "token_ffn_worklist")
+    P, dev = bits.numel(), bits.device
+    if (T + 1) * P >= 1 << 31:
+        raise _lib.M3Error(f"token_ffn_worklist: (T + 1) * B*N = {(T + 1) * P} must stay below 2^31")
+    w = TokenWorkList()
+    w.P, w.T, w.mode, w.M_ub = P, T, mode, token_ffn_rows_ub(P, T, mode)
+    w.rows = torch.empty(w.M_ub, dtype=torch.int32, device=dev) if rows is None else _req(rows, torch.int32, "rows", numel=w.M_ub)
+    w.slot_of = (torch.empty((T + 1, P), dtype=torch.int32, device=dev) if slot_of is None
+                 else _req(slot_of, torch.int32, "slot_of", numel=(T + 1) * P))
+    meta = torch.empty(8, dtype=torch.int32, device=dev)
+    w.offsets, w.tile_starts, w.count = meta[0:2], meta[2:4], meta[4:5]
+    n_ws = int(lib().m3_token_ffn_list_ws_elems(P, T))
+    if ws is None:
+        ws = torch.empty(n_ws, dtype=torch.int32, device=dev)
+    _req(ws, torch.int32, "ws", min_numel=n_ws)
+    check(lib().m3_token_ffn_worklist(_p(bits), P, T, _token_ffn_mode(mode), _p(w.rows), _p(w.slot_of), _p(w.offsets),
+                                      _p(w.tile_starts), _p(w.count), _p(ws), _stream()), "m3_token_ffn_worklist")
+    return w
+
+
+def _token_ffn_common(xs, sx, w: TokenWorkList, what):
+    xs, P, D, _ = _share_common(xs, None, None, what)
+    if len(xs) != w.T or P != w.P:
+        raise _lib.M3Error(f"{what}: {len(xs)} task tensors of {P} positions, the work list was built for {w.T} of {w.P}")
+    if sx is not None:
+        _req(sx, xs[0].dtype, "shared_x", numel=P * D)
+    return xs, P, D
+
+
+def token_ffn_ln_fwd(xs, sx, w: TokenWorkList, gamma, beta, eps=1e-6, *, h=None, mean=None, rstd=None):
+    """m3_token_ffn_ln_fwd: (h [M_ub, D] in the activation dtype, mean f32 [M_ub], rstd f32 [M_ub]); rows at and past the
+    work list's count are left as they are"""
+    xs, P, D = _token_ffn_common(xs, sx, w, "token_ffn_ln_fwd")
+    dt, dev = xs[0].dtype, xs[0].device
+    _req(gamma, torch.float32, "gamma", numel=D); _req(beta, torch.float32, "beta", numel=D)
+    h = torch.empty((w.M_ub, D), dtype=dt, device=dev) if h is None else _req(h, dt, "h", numel=w.M_ub * D)
+    mean = torch.empty(w.M_ub, dtype=torch.float32, device=dev) if mean is None else _req(mean, torch.float32, "mean", numel=w.M_ub)
+    rstd = torch.empty(w.M_ub, dtype=torch.float32, device=dev) if rstd is None else _req(rstd, torch.float32, "rstd", numel=w.M_ub)
+    xr = _share_rows(xs, P, D, dt, "x")
+    check(lib().m3_token_ffn_ln_fwd(byref(xr), _p(sx), dt_code(dt), w.T, P, D, _p(w.rows), _p(w.count), w.M_ub, _p(gamma),
+                                    _p(beta), float(eps), _p(h), _p(mean), _p(rstd), _stream()), "m3_token_ffn_ln_fwd")
+    return h, mean, rstd
+
+
+def _token_ffn_scales(path_scale, shared_path_scale, P, N, what):
+    if N < 1 or P % N:
+        raise _lib.M3Error(f"{what}: N={N} tokens per sample must divide B*N={P}")
+    if path_scale is not None:
+        _req(path_scale, torch.float32, "path_scale", numel=P // N)
+    if shared_path_scale is not None:
+        _req(shared_path_scale, torch.float32, "shared_path_scale", numel=P)
+
+
+def token_ffn_scatter_fwd(xs, sx, f, w: TokenWorkList, bits, N, path_scale=None, shared_path_scale=None, *, ys=None):
+    """m3_token_ffn_scatter_fwd: the list of y_t.  f [M_ub, D]: the FFN of the work rows; N: tokens per sample (path_scale f32
+    [P / N]); shared_path_scale f32 [P]; None = 1."""
+    xs, P, D = _token_ffn_common(xs, sx, w, "token_ffn_scatter_fwd")
+    dt = xs[0].dtype
+    _req(f, dt, "f", numel=w.M_ub * D); _req(bits, torch.int64, "shared_bits", numel=P)
+    _token_ffn_scales(path_scale, shared_path_scale, P, N, "token_ffn_scatter_fwd")
+    xr = _share_rows(xs, P, D, dt, "x")
+    ys = [torch.empty_like(x) for x in xs] if ys is None else ys
+    yr = _share_rows(ys, P, D, dt, "y")
+    check(lib().m3_token_ffn_scatter_fwd(byref(xr), _p(sx), _p(f), dt_code(dt), w.T, P, N, D, _token_ffn_mode(w.mode),
+                                         _p(w.slot_of), _p(bits), _p(path_scale), _p(shared_path_scale), byref(yr), _stream()),
+          "m3_token_ffn_scatter_fwd")
+    return ys
+
+
+def token_ffn_gather_bwd(dys, w: TokenWorkList, bits, N, path_scale=None, shared_path_scale=None, *, df=None):
+    """m3_token_ffn_gather_bwd: d f [M_ub, D] from the d y_t list; rows at and past the count are left as they are"""
+    dys, P, D = _token_ffn_common(dys, None, w, "token_ffn_gather_bwd")
+    dt = dys[0].dtype
+    _req(bits, torch.int64, "shared_bits", numel=P)
+    _token_ffn_scales(path_scale, shared_path_scale, P, N, "token_ffn_gather_bwd")
+    df = torch.empty((w.M_ub, D), dtype=dt, device=dys[0].device) if df is None else _req(df, dt, "df", numel=w.M_ub * D)
+    dyr = _share_rows(dys, P, D, dt, "dy")
+    check(lib().m3_token_ffn_gather_bwd(byref(dyr), dt_code(dt), w.T, P, N, D, _p(w.rows), _p(w.count), w.M_ub, _p(bits),
+                                        _p(path_scale), _p(shared_path_scale), _p(df), _stream()), "m3_token_ffn_gather_bwd")
+    return df
+
+
+def token_ffn_bwd_ws_elems(P, D) -> int:
+    return int(lib().m3_token_ffn_bwd_ws_elems(P, D))
+
+
+def token_ffn_scatter_bwd(xs, sx, dys, dh, mean, rstd, w: TokenWorkList, bits, gamma, *, dxs=None, d_sx=None, ws=None):
+    """m3_token_ffn_scatter_bwd: (d x_t list, d shared_x [P, D], d gamma f32 [D], d beta f32 [D])"""
+    xs, P, D = _token_ffn_common(xs, sx, w, "token_ffn_scatter_bwd")
+    dt, dev = xs[0].dtype, xs[0].device
+    _req(dh, dt, "dh", numel=w.M_ub * D)
+    _req(mean, torch.float32, "mean", numel=w.M_ub); _req(rstd, torch.float32, "rstd", numel=w.M_ub)
+    _req(bits, torch.int64, "shared_bits", numel=P); _req(gamma, torch.float32, "gamma", numel=D)
+    xr = _share_rows(xs, P, D, dt, "x")
+    dyr = _share_rows(list(dys), P, D, dt, "dy")
+    dxs = [torch.empty_like(x) for x in xs] if dxs is None else dxs
+    dxr = _share_rows(dxs, P, D, dt, "dx")
+    d_sx = torch.empty((P, D), dtype=dt, device=dev) if d_sx is None else _req(d_sx, dt, "d_shared_x", numel=P * D)
+    n_ws = token_ffn_bwd_ws_elems(P, D)
+    if ws is None:
+        ws = torch.empty(max(n_ws, 4), dtype=torch.float32, device=dev)
+    _req(ws, torch.float32, "ws", min_numel=n_ws)
+    dg = torch.empty(D, dtype=torch.float32, device=dev)
+    db = torch.empty(D, dtype=torch.float32, device=dev)
+    check(lib().m3_token_ffn_scatter_bwd(byref(xr), _p(sx), byref(dyr), _p(dh), _p(mean), _p(rstd), dt_code(dt), w.T, P, D,
+                                         _token_ffn_mode(w.mode), _p(w.slot_of), _p(bits), _p(gamma), byref(dxr), _p(d_sx),
+                                         _p(ws), _p(dg), _p(db), _stream()), "m3_token_ffn_scatter_bwd")
+    return dxs, d_sx, dg, db

@@ -7,6 +7,10 @@ csrc/share.hip, with the reference's names, constructor arguments, parameter nam
   transition_stage, apply_shared_broadcast      TokenBlock's methods, token/vision_transformer_moe.py:519-671, as functions
   SharingStage                                  predictor + transition + broadcast of TokenBlock.forward (:873-959) fused: one
                                                 row pass, one autograd node, no host read, graph-capturable
+  TokenFFNStage                                 step 5 of TokenBlock.forward for the blocks that need no router: the dense
+                                                block's dense_mlp_stage + shared_dense_forward + apply_shared_broadcast
+                                                (:443-515, :966-984), or the shared_ffn branch of an MoE block (:1002-1014),
+                                                over private and shared rows only (csrc/token_ffn.hip)
 
 Differences from the reference, all on purpose:
   * no host read in SharingStage, Aggregation, AggregationStage or SharingRegularizationLoss: no nonzero(), .any() or
@@ -28,10 +32,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .functional import ShareAggregateFn, SharePredictFn, ShareStageFn
+from .functional import ShareAggregateFn, SharePredictFn, ShareStageFn, TokenFFNFn
 
 __all__ = ["ShareabilityPredictor", "Aggregation", "AggregationStage", "SharingRegularizationLoss", "SharingStage",
-           "SharedTokens", "transition_stage", "apply_shared_broadcast"]
+           "SharedTokens", "TokenFFNStage", "transition_stage", "apply_shared_broadcast"]
 
 _STAT = {k[len("M3_SHARE_STAT_"):].lower(): v for k, v in _lib.CONSTANTS.items() if k.startswith("M3_SHARE_STAT_")}
 
@@ -259,6 +263,97 @@ class SharingStage(nn.Module):
         for t, y in enumerate(ys):
             out[t] = y
         return out, SharedTokens(bits.view(B, N), sx, idx, count, g.view(T, B, N), stats, T)
+
+
+class TokenFFNStage(nn.Module):
+    """TokenBlock.forward's step 5 where no router is needed, as one autograd node over the rows that differ:
+      mode "all"     the dense block: outs = dense_mlp_stage(outs, shared_bits); shared_out = shared_dense_forward(shared_x);
+                     outs = apply_shared_broadcast(outs, shared_bits, shared_out) - private rows and one row per shared
+                     position through ONE norm2 / mlp, one FC1 and one FC2 launch for all of them
+      mode "shared"  the MoE block's shared branch: shared_out = shared_x + drop_path(shared_ffn(norm2(shared_x))), then the
+                     broadcast; private rows pass through (they are the router's)
+    Holds the caller's nn.LayerNorm and Mlp (a TokenBlock's norm2 and mlp / shared_ffn), as SharingStage holds its predictor:
+    its state-dict keys are the block's own: norm2.*, mlp.fc1.*, mlp.fc2.* (mode "shared": norm2.*, shared_ffn.fc1.*, shared_ffn.fc2.*).  A position shared by s
+    tasks costs one FFN row, not s; the row count stays on the device: no host read, fixed shapes, the caller's stream,
+    graph-capturable.  Refused (M3Error): Mlp.drop.p > 0 in training, an activation other than the erf GELU, num_tasks outside
+    2 .. 8, C or H no multiple of 8, C > 1024, CPU tensors, and whatever the GEMM's own reach rule refuses."""
+
+    def __init__(self, norm2: nn.LayerNorm, mlp: nn.Module, num_tasks: int, mode: str = "all", drop_path: float = 0.0):
+        super().__init__()
+        if not 2 <= num_tasks <= ops.SHARE_MAX_T:
+            raise _lib.M3Error(f"TokenFFNStage: num_tasks={num_tasks}; the token kernels take 2 to {ops.SHARE_MAX_T} tasks")
+        if mode not in ops.TOKEN_FFN_MODES:
+            raise _lib.M3Error(f"TokenFFNStage: mode {mode!r} is neither 'all' nor 'shared'")
+        if not isinstance(norm2, nn.LayerNorm) or len(norm2.normalized_shape) != 1 or norm2.weight is None or norm2.bias is None:
+            raise _lib.M3Error("TokenFFNStage: norm2 must be an nn.LayerNorm over the last dimension with weight and bias")
+        act = getattr(mlp, "act", None)
+        if not isinstance(act, nn.GELU) or getattr(act, "approximate", "none") != "none":
+            raise _lib.M3Error(f"TokenFFNStage: the activation is {type(act).__name__}; the FC1 epilogue computes the erf GELU only")
+        C, H = mlp.fc1.in_features, mlp.fc1.out_features
+        if norm2.normalized_shape[0] != C or mlp.fc2.in_features != H or mlp.fc2.out_features != C:
+            raise _lib.M3Error(f"TokenFFNStage: norm2 {tuple(norm2.normalized_shape)}, fc1 {C} -> {H}, fc2 {mlp.fc2.in_features} -> "
+                               f"{mlp.fc2.out_features} do not make a residual FFN")
+        if mlp.fc1.bias is None or mlp.fc2.bias is None:
+            raise _lib.M3Error("TokenFFNStage: fc1 and fc2 must have a bias, as the reference's Mlp")
+        if C % 8 or H % 8 or not 8 <= C <= ops.SHARE_MAX_D:
+            raise _lib.M3Error(f"TokenFFNStage: C={C} and H={H} must be multiples of 8 and C at most {ops.SHARE_MAX_D}")
+        if not 0.0 <= float(drop_path) < 1.0:
+            raise _lib.M3Error(f"TokenFFNStage: drop_path={drop_path} outside [0, 1)")
+        self.norm2 = norm2
+        self.add_module(self._ffn_name(mode), mlp)       # the TokenBlock's name for it: mlp, or shared_ffn in an MoE block
+        self.num_tasks, self.mode, self.drop_path = num_tasks, mode, float(drop_path)
+
+    @staticmethod
+    def _ffn_name(mode):
+        return "mlp" if mode == "all" else "shared_ffn"
+
+    @property
+    def ffn(self):
+        return getattr(self, self._ffn_name(self.mode))
+
+    def _drop_p(self):
+        d = getattr(self.ffn, "drop", None)
+        return float(getattr(d, "p", 0.0) or 0.0)
+
+    def forward(self, outs, shared: "SharedTokens | None" = None, path_scale=None, shared_path_scale=None):
+        """outs {t: [B, N, C]} (SharingStage's, the broadcast already applied); shared: its SharedTokens, or None = nothing
+        is shared (the reference's shared_bits=None); path_scale f32 [B] / shared_path_scale f32 [B, N] or [B*N]: the DropPath
+        factors of the private rows (one per sample and block) and of the shared rows (one per shared row), None = 1 - or, in
+        training with drop_path > 0, drawn on the device.  Returns a new dictionary (or list)."""
+        T = self.num_tasks
+        if self.training and self._drop_p() > 0.0:
+            raise _lib.M3Error(f"TokenFFNStage: Mlp.drop.p={self._drop_p()} in training; element-wise dropout is not built on this path")
+        xs = _tasks(outs, T, "TokenFFNStage")
+        B, N, C = xs[0].shape
+        if C != self.ffn.fc1.in_features:
+            raise _lib.M3Error(f"TokenFFNStage: tokens of width {C}, the Mlp takes {self.ffn.fc1.in_features}")
+        dev = xs[0].device
+        if shared is None:
+            bits = torch.zeros(B * N, dtype=torch.int64, device=dev)
+            sx = torch.zeros((B * N, C), dtype=xs[0].dtype, device=dev)
+        else:
+            bits = _gpu(shared.bits, "shared.bits").contiguous().reshape(-1)
+            sx = _gpu(shared.x, "shared.x")
+            if bits.dtype != torch.int64 or bits.numel() != B * N or sx.shape != (B * N, C) or sx.dtype != xs[0].dtype:
+                raise _lib.M3Error(f"TokenFFNStage: shared.bits {bits.dtype} {tuple(shared.bits.shape)} / shared.x {sx.dtype} "
+                                   f"{tuple(sx.shape)} do not go with outs {xs[0].dtype} {(B, N, C)}")
+        if self.training and self.drop_path > 0.0:
+            keep = 1.0 - self.drop_path
+            if path_scale is None and self.mode == "all":
+                path_scale = torch.floor(keep + torch.rand(B, dtype=torch.float32, device=dev)) / keep
+            if shared_path_scale is None:
+                shared_path_scale = torch.floor(keep + torch.rand(B * N, dtype=torch.float32, device=dev)) / keep
+        if path_scale is not None:
+            path_scale = _gpu(path_scale, "path_scale").to(torch.float32).reshape(-1).contiguous()
+        if shared_path_scale is not None:
+            shared_path_scale = _gpu(shared_path_scale, "shared_path_scale").to(torch.float32).reshape(-1).contiguous()
+        ys = TokenFFNFn.apply(bits, self.norm2.weight, self.norm2.bias, float(self.norm2.eps), self.ffn.fc1.weight,
+                              self.ffn.fc1.bias, self.ffn.fc2.weight, self.ffn.fc2.bias, path_scale, shared_path_scale,
+                              self.mode, N, sx, *xs)
+        out = dict(outs) if isinstance(outs, dict) else list(outs)
+        for t, y in enumerate(ys):
+            out[t] = y
+        return out
 
 
 def transition_stage(outs, prev_shared_bits, g_shared, gamma=0.5, eps=1e-6, num_tasks=None):
